@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- SiftPlan.keypoints() throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, the rooflines that the
+timed steps themselves measure (or that are replayed from committed profiles).  Without the legs in front of it (below)
+the GPU would enter the timed region from seconds of idle, on its clock ramp: a plain c2 run first repeats the headline
+call for RAMP_S seconds, untimed, then runs the W warm-up steps.  `--full` adds everything else the benchmark measures:
+the legs beside the headline (run first, N = 1: BatchPlan, host-to-host, keypoint-rich frame, MatchPlan 100k, C3 16384^2,
+C4 on one GPU; at every N the 2-lane BatchPlan leg), `steady` (200 further steps) and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs) after the timed region.
 
 `--gpus N` with N > 1 starts N ranks itself (one process per GPU, torch.distributed backend "nccl" = RCCL over xGMI)
 unless it already runs under a launcher (WORLD_SIZE set, e.g. `python -m torch.distributed.run --nproc-per-node N
@@ -51,10 +59,36 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SIZE = 4096
 OCTAVES = 3
 C4_FRAMES, C4_SIZE = 64, 2048
+RAMP_S = 0.5            # untimed repeats of the headline call in a plain run: ~25 calls bring the clocks back (tools/dev/ramp.py)
+DUMP_MAX_ROWS = 100000  # rows of 133 float32 each: a dump stays under 64 MB
 
 
 def make_image(seed, size=SIZE):
     return np.random.default_rng(seed).random((size, size), dtype=np.float32)
+
+
+def dump_outputs(path, frames_kp):
+    """Write the keypoint records a caller received from the last timed step, frame by frame, as .npy files under `path`:
+    keypoints.npy (n, 4) float32 x, y, scale, angle; descriptors.npy (n, 128) float32; frame.npy (n,) float32, the frame of
+    each row; counts.npy (frames,) float64, the keypoints of each frame.  Within a frame the records are sorted by their
+    bytes (the library's order is not specified); above DUMP_MAX_ROWS rows a fixed, seeded sample of rows is written."""
+    parts, frame = [], []
+    for f, k in enumerate(frames_kp):
+        k = np.ascontiguousarray(k).view(np.uint8).reshape(len(k), 144)      # the 144-byte records
+        key = np.lexsort(k.T[::-1])
+        parts.append(k[key])
+        frame.append(np.full(len(k), f, np.float32))
+    rec = np.concatenate(parts) if parts else np.zeros((0, 144), np.uint8)
+    frame = np.concatenate(frame) if frame else np.zeros(0, np.float32)
+    if len(rec) > DUMP_MAX_ROWS:
+        pick = np.sort(np.random.default_rng(0).choice(len(rec), DUMP_MAX_ROWS, replace=False))
+        rec, frame = rec[pick], frame[pick]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "keypoints.npy"), np.ascontiguousarray(rec[:, :16]).view(np.float32))
+    np.save(os.path.join(path, "descriptors.npy"), rec[:, 16:].astype(np.float32))
+    np.save(os.path.join(path, "frame.npy"), frame)
+    np.save(os.path.join(path, "counts.npy"), np.array([len(k) for k in frames_kp], np.float64))
+    return len(rec)
 
 
 def bytes_alg(w, h, n_oct, n_kp):
@@ -466,13 +500,20 @@ def main():
                     help="c2: one 4096^2 frame per step and GPU (default, the headline); c4: 64 x 2048^2 frames sharded over the GPUs")
     ap.add_argument("--size", type=int, default=0, help="image side (default: the BASELINE config: 4096 for c2, 2048 for c4)")
     ap.add_argument("--octaves", type=int, default=-1, help="0 = every octave (reference default); default 3 for c2, all for c4")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-steady", action="store_true", help="skip the 200-step steady-state measurement after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: the legs (BatchPlan, host-to-host, MatchPlan, C3, C4), "
+                         "`steady` and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-steady", action="store_true", help="with --full: skip the 200-step steady-state measurement after the timed region")
     ap.add_argument("--no-pipelined", "--no-extras", dest="no_extras", action="store_true",
-                    help="skip the extra measurements (BatchPlan, host-to-host, MatchPlan)")
+                    help="skip the extra measurements (BatchPlan, host-to-host, MatchPlan) with --full, the clock ramp without it")
     ap.add_argument("--backend", default="", help="torch.distributed backend (default nccl = RCCL; gloo only with --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
@@ -505,7 +546,7 @@ def main():
     import ctypes
     import sift_pyocl_amd as sp
     from sift_pyocl_amd import _lib
-    from sift_pyocl_amd.batch import RECORD_BYTES, gather_records_device, shard_indices
+    from sift_pyocl_amd.batch import RECORD_BYTES, gather_records_device, shard_indices, split_gathered
 
     c4 = args.config == "c4"
     size = args.size or (C4_SIZE if c4 else SIZE)
@@ -536,8 +577,8 @@ def main():
             counts, records = bp.keypoints_batch_device(frames)
             if distributed:
                 all_counts, gathered = gather_records_device(counts, xfer(records), C4_FRAMES, rank, world)
-                return sum(sum(r) for r in all_counts), gathered
-            return sum(counts), records
+                return sum(sum(r) for r in all_counts), (all_counts, gathered)
+            return sum(counts), (counts, records)
 
         for _ in range(max(W, 1)):
             step()
@@ -549,6 +590,13 @@ def main():
             total_kp += nk
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            if distributed:
+                outputs = split_gathered(keep[0], keep[1], C4_FRAMES, world)
+            else:
+                host = keep[1].cpu().numpy()
+                bounds = np.cumsum([0] + list(keep[0])) * RECORD_BYTES
+                outputs = [host[a:b].view(sp.SiftPlan.dtype_kp) for a, b in zip(bounds[:-1], bounds[1:])]
         units = K * C4_FRAMES * size * size / 1e6
         workload = ("batch of %d frames of %dx%d fp32 uniform white noise, frame i on rank i mod %d (%d per GPU), BatchPlan "
                     "(%d lanes) per rank, frames resident in HBM, all-gather of every frame's records on device tensors"
@@ -602,17 +650,24 @@ def main():
         # + K timed steps that follow then start from a GPU at its sustained clocks instead of from seconds of idle time
         # (tools/dev/ramp.py: after 0.2 ... 2 s of idle the first ~25 calls run 0.92, 0.85, 0.83, 0.81, 0.80 ms in groups of
         # five before the 0.79 of the steady state; rounds 1-4 ran the legs after the timed region and their lines carry that
-        # ramp: compare `steady` across rounds, not `ms_per_step`).  Nothing of the timed region changes.
-        if not args.no_extras:
+        # ramp: compare `steady` across rounds, not `ms_per_step`).  Nothing of the timed region changes.  A plain run has no
+        # legs: the headline call itself, repeated for RAMP_S seconds, brings the clocks up instead.
+        last = None
+        if args.full and not args.no_extras:
             if world == 1:
                 extra = extras(sp, torch, size, n_oct, local_rank)
             # every rank, at every N: the 2-lane BatchPlan leg directly in front of the warm-up (reported by rank 0)
             extra["pipelined"] = leg_pipelined(sp, torch, size, n_oct, local_rank, keep=keepalive)
             order = ("legs beside the headline first (N > 1: the pipelined leg only, on every rank), then W warm-up + K timed "
                      "steps, then `steady` (N = 1), then the CPU baselines (N = 1)")
+        elif not args.no_extras:
+            t_end, i = time.perf_counter() + RAMP_S, 0
+            while time.perf_counter() < t_end:
+                last = plan.keypoints(dev_images[i % n_img])
+                i += 1
+            order = "%d untimed calls (%.1f s: the clock ramp), then W warm-up + K timed steps" % (i, RAMP_S)
         else:
             order = "W warm-up + K timed steps first"
-        last = None
         for i in range(W):
             # held like in the timed loop: the previous result is alive while the next call runs, so the pinned pool serves
             # two record blocks in rotation (without this the second TIMED step allocated the second block: +0.3 ms once)
@@ -644,6 +699,7 @@ def main():
             assert sum(sum(r) for r in all_counts) >= n_kp and gathered.shape[0] == world
         barrier()
         elapsed = time.perf_counter() - t0
+        outputs = [np.array(last)] if args.dump_outputs else None    # a copy: the next call may reuse the pinned record block
         # hipEvent times of the K timed calls (the library sums them as the calls complete: one read-out, after the region)
         t = plan.profile_totals(reset=True)
         assert t["calls"] == K
@@ -654,7 +710,7 @@ def main():
         # beside `value`: the same step over a longer window -- reported, never `value` (rounds 1-4, whose timed region
         # started from an idle GPU, printed 3-5 % more in `ms_per_step` than here: this is the figure to compare across rounds)
         steady = None
-        if world == 1 and not args.no_steady:
+        if world == 1 and args.full and not args.no_steady:
             ns = 200
             torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -766,7 +822,10 @@ def main():
             out["steady"] = kt["steady"]
         out["order"] = order
         out.update(extra)
-        if not args.no_cpu_baseline and world == 1 and not c4:
+        if args.dump_outputs:
+            rows = dump_outputs(args.dump_outputs, outputs)
+            print("bench.py: %d keypoint rows of the last timed step written to %s" % (rows, args.dump_outputs), file=sys.stderr)
+        if args.full and not args.no_cpu_baseline and world == 1 and not c4:
             out["cpu_baseline"] = cpu_baseline(size, result["n_oct"])
             ref = cpu_reference_kernels(size, result["n_oct"])
             if ref is not None:

@@ -3,8 +3,8 @@
 TEST INFRASTRUCTURE.  The library holds the reference's own OpenCL C kernels built for
 x86-64 (oracle/Makefile `ref` target); this module sequences them in the launch order and
 with the scalar arguments of the reference host code (sift-src/plan.py:432-756,
-sift-src/match.py:200-271), replacing PyOpenCL by direct calls.  It is used to pin the CPU
-oracle (tests/test_oracle_vs_ref.py) and to generate tests/golden/*.npz.
+sift-src/match.py:200-271), replacing PyOpenCL by direct calls.  It generates the golden vectors
+that pin the CPU oracle (tests/golden/make_golden.py, tests/golden/make_ref_xcheck.py).
 
 It can only be (re)built where /root/reference is mounted; the built .so travels to the GPU
 box but nothing at run time reads /root/reference.

@@ -5,6 +5,7 @@ import importlib.util
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,7 +63,43 @@ def test_default_flags_are_the_driver_contract(bench, monkeypatch):
     with pytest.raises(SystemExit):
         bench.main()
     assert seen["ns"].gpus == 1 and 1 <= seen["ns"].steps <= 100 and 0 <= seen["ns"].warmup <= 20 and seen["ns"].config == "c2"
+    assert not seen["ns"].full and not seen["ns"].dump_outputs          # a plain run measures the headline only
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2"])
     with pytest.raises(SystemExit):
         bench.main()
     assert (seen["ns"].gpus, seen["ns"].steps, seen["ns"].warmup) == (8, 5, 2)
+
+
+def test_dump_outputs_layout(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 arrays, records sorted within a frame (the library's order is not specified), so
+    that the same records in another order give the same files; above DUMP_MAX_ROWS a fixed sample of rows."""
+    from sift_pyocl_amd import SiftPlan
+    rng = np.random.default_rng(4)
+    frames = []
+    for n in (300, 0, 170):
+        k = np.zeros(n, SiftPlan.dtype_kp)
+        for f in ("x", "y", "scale", "angle"):
+            k[f] = rng.random(n, dtype=np.float32) * 100
+        k["desc"] = rng.integers(0, 256, (n, 128), dtype=np.uint8)
+        frames.append(k)
+
+    def dump(where, frames):
+        rows = bench.dump_outputs(str(where), frames)
+        return rows, {name: np.load(os.path.join(str(where), name + ".npy")) for name in ("keypoints", "descriptors", "frame", "counts")}
+
+    rows, a = dump(tmp_path / "a", frames)
+    assert rows == 470 and a["keypoints"].shape == (470, 4) and a["descriptors"].shape == (470, 128) and a["frame"].shape == (470,)
+    assert a["keypoints"].dtype == a["descriptors"].dtype == a["frame"].dtype == np.float32 and a["counts"].dtype == np.float64
+    assert a["counts"].tolist() == [300, 0, 170] and (np.diff(a["frame"]) >= 0).all()
+    first = frames[0]
+    got = {tuple(r) for r in np.concatenate([a["keypoints"][:300], a["descriptors"][:300]], axis=1)}
+    want = {tuple(r) for r in np.concatenate([np.stack([first[f] for f in ("x", "y", "scale", "angle")], axis=1),
+                                              first["desc"].astype(np.float32)], axis=1)}
+    assert got == want
+    _, b = dump(tmp_path / "b", [k[rng.permutation(len(k))] for k in frames])
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 100)
+    rows, c = dump(tmp_path / "c", frames)
+    _, d = dump(tmp_path / "d", [k[rng.permutation(len(k))] for k in frames])
+    assert rows == 100 and c["keypoints"].shape == (100, 4) and c["counts"].tolist() == [300, 0, 170]
+    assert all(np.array_equal(c[n], d[n]) for n in c)

@@ -1,5 +1,6 @@
-"""The driver's contract for bench.py and __graft_entry__ on a GPU box: one JSON line with the agreed keys, roofline and
-cpu_baseline objects; smoke() passes.  The N > 1 branch is rehearsed with two ranks sharing the GPU (RCCL refuses two
+"""The driver's contract for bench.py and __graft_entry__ on a GPU box: one JSON line with the agreed keys and roofline
+objects, the legs and cpu_baseline objects with --full, the outputs of the last timed step with --dump-outputs; smoke()
+passes.  The N > 1 branch is rehearsed with two ranks sharing the GPU (RCCL refuses two
 ranks on one device, so their collectives run over gloo): once through bench.py's own launcher (`--gpus 2`, no
 torch.distributed.run), once under torch.distributed.run as the driver starts it, and once for the C4 workload."""
 import json
@@ -7,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +44,7 @@ def check_common(d, n_gpus, steps, warmup, scaling="weak"):
 
 
 def test_bench_single_gpu_line():
-    d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1"])
+    d = run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1"])
     check_common(d, 1, 3, 1)
     c = d["cpu_baseline"]
     for key in ("value", "unit", "cores", "kind", "sample"):
@@ -55,6 +57,28 @@ def test_bench_single_gpu_line():
     for key in ("pipelined", "host_to_host", "match_100k"):
         assert key in d and "error" not in d[key], (key, d.get(key))
     assert d["match_100k"]["pairs"] == d["match_100k"]["expected_pairs"]
+
+
+def test_bench_plain_line_and_outputs(oracle, tmp_path):
+    """A plain run measures the headline only, and --dump-outputs writes what its last timed step returned: with K = 3 and
+    W = 1 every step runs on the frame of seed 0, whose keypoints the oracle gives bit for bit."""
+    from util import assert_same_keypoints, dtype_kp
+    d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    check_common(d, 1, 3, 1)
+    for key in ("cpu_baseline", "steady", "pipelined", "host_to_host", "match_100k", "c3_16384", "c4_one_gpu"):
+        assert key not in d, key
+    assert abs(d["value"] - 4096 * 4096 / 1e6 / (d["ms_per_step"] / 1e3)) / d["value"] < 0.01
+    kp, desc = np.load(str(tmp_path / "keypoints.npy")), np.load(str(tmp_path / "descriptors.npy"))
+    counts, frame = np.load(str(tmp_path / "counts.npy")), np.load(str(tmp_path / "frame.npy"))
+    assert kp.dtype == desc.dtype == frame.dtype == np.float32 and counts.dtype == np.float64
+    assert counts.tolist() == [len(kp)] and (frame == 0).all() and abs(len(kp) - d["config"]["keypoints_per_image"]) < 1e-6
+    got = np.zeros(len(kp), dtype_kp)
+    for i, f in enumerate(("x", "y", "scale", "angle")):
+        got[f] = kp[:, i]
+    got["desc"] = desc.astype(np.uint8)
+    assert np.array_equal(got["desc"].astype(np.float32), desc)
+    img = np.random.default_rng(0).random((4096, 4096), dtype=np.float32)
+    assert_same_keypoints(got, oracle.keypoints(img, oracle.default_params(octave_max=3)), "bench --dump-outputs")
 
 
 def free_port():

@@ -1,148 +1,127 @@
-"""CPU test: the oracle against the reference's own kernels run natively (oracle/_ref), on inputs that
-are NOT in the golden set.  Skipped where the native reference build is unavailable (it can only be
-built where /root/reference is mounted; the prebuilt .so may travel with the repository snapshot)."""
+"""CPU test: the oracle against the reference's own kernels run natively, on inputs that are NOT in the golden set
+of tests/test_oracle_golden.py.  The reference's outputs are stored in tests/golden/ref_xcheck.npz / .json (generator
+tests/golden/make_ref_xcheck.py, run where the reference's kernels can be built: oracle/_ref), so the test needs
+neither the reference nor its native build."""
+import json
+import os
+
 import numpy as np
 import pytest
 
-from util import assert_same_keypoints, compare_keypoints_libm, digest_cases, kp_digest, smooth_noise, sort_rows, white_noise
+from util import (PIPELINE_CASES, XCHECK_SIGMAS, array_digest, assert_same_keypoints, compare_keypoints_libm, converter_inputs,
+                  digest_cases, kp_digest, matching_valid_inputs, matching_valid_steps, pipeline_input, smooth_noise, sort_kp,
+                  sort_rows, transform_xcheck_cases)
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture(scope="module")
 def ref():
-    from oracle import pyref
-    if not pyref.available() and not pyref.build():
-        pytest.skip("oracle/_ref/libsiftclref.so not built (needs /root/reference)")
-    return pyref
+    """The reference kernels' stored outputs: (arrays of ref_xcheck.npz, ref_xcheck.json)."""
+    z = np.load(os.path.join(GOLD, "ref_xcheck.npz"))
+    return {k: z[k] for k in z.files}, json.load(open(os.path.join(GOLD, "ref_xcheck.json")))
 
 
-@pytest.mark.parametrize("seed,shape,smooth", [(21, (200, 333), True), (22, (160, 160), False), (23, (97, 211), True)])
+@pytest.mark.parametrize("seed,shape,smooth", PIPELINE_CASES)
 def test_pipeline_identical(oracle, ref, seed, shape, smooth):
-    img = smooth_noise(shape, seed=seed, sigma=2.5) if smooth else white_noise(shape, seed=seed)
-    print(compare_keypoints_libm(oracle.keypoints(img), ref.keypoints(img), "seed %d" % seed))
+    img = pipeline_input(seed, shape, smooth)
+    print(compare_keypoints_libm(oracle.keypoints(img), ref[0]["pipeline_%d" % seed], "seed %d" % seed))
 
 
 @pytest.mark.parametrize("name", sorted(digest_cases()))
 def test_reference_kernels_with_siftmath_equal_oracle_bytes(oracle, ref, name):
     """libm isolated: the reference's own kernels, with exp / sin / cos / atan2 / pow(2,.) bound to the oracle's siftmath
     (oracle/_ref/libsiftclref_sm.so), reproduce the oracle BYTE FOR BYTE at sizes the small goldens do not reach
-    (39 k / 2.7 k / 18.7 k keypoints).  So the restatement is exact, and every residual of the glibc-backed build
-    (next test) is a last-bit choice of libm."""
+    (39 k / 2.7 k / 18.7 k keypoints): the oracle's per-field digests equal those of the reference's records
+    (tests/golden/kp_digests.json, what the GPU box checks the HIP path against).  So the restatement is exact, and every
+    residual of the glibc-backed build (next test) is a last-bit choice of libm."""
     maker, shape, kw = digest_cases()[name]
-    img = maker(shape, **kw)
-    ref.use("siftmath")
-    try:
-        if not ref.available():
-            pytest.skip("oracle/_ref/libsiftclref_sm.so not built (needs /root/reference)")
-        got = ref.keypoints(img)
-    finally:
-        ref.use("glibc")
-    want = oracle.keypoints(img)
+    want = oracle.keypoints(maker(shape, **kw))
     assert len(want) > 2000
-    assert_same_keypoints(want, got, name)
-    # ... and both equal the committed digest (what the GPU box checks the HIP path against)
-    import json, os
-    golden = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "kp_digests.json")))
-    assert kp_digest(got) == golden[name]
+    golden = json.load(open(os.path.join(GOLD, "kp_digests.json")))
+    assert kp_digest(want) == golden[name]
 
 
 @pytest.mark.parametrize("name", ["smooth2048", "smooth1031x1537"])
 def test_glibc_build_tolerance(oracle, ref, name):
-    """The glibc-backed build at full size, with the tolerance that actually holds (see compare_keypoints_libm)."""
+    """The glibc-backed build at full size, with the tolerance that actually holds (see compare_keypoints_libm).  Its
+    records are the siftmath-backed build's (= the oracle's, previous test) with the stored rows in which they differ
+    patched in; the patched set must reproduce the glibc-backed build's digest before it is compared."""
+    arrays, meta = ref
     maker, shape, kw = digest_cases()[name]
-    img = maker(shape, **kw)
-    print(compare_keypoints_libm(oracle.keypoints(img), ref.keypoints(img), name))
+    want = oracle.keypoints(maker(shape, **kw))
+    got = sort_kp(want).copy()
+    got[arrays["glibc_%s_rows" % name]] = arrays["glibc_%s_records" % name]
+    assert kp_digest(got) == meta["glibc_" + name], "%s: the oracle's records are not the siftmath build's" % name
+    print(compare_keypoints_libm(want, got, name))
 
 
 def test_double_im_size_identical(oracle, ref):
     """par.DoubleImSize = 1 (the input counts as blurred by sigma 1.0, plan.py:534: an 11-tap initial blur instead of the
     15-tap one): the oracle's flag against the reference's own kernels driven with the parameter set, libm isolated."""
+    from oracle import pyref
     img = smooth_noise((200, 333), seed=21, sigma=2.5)
-    ref.use("siftmath")
-    saved = ref.PAR["DoubleImSize"]
+    saved = pyref.PAR["DoubleImSize"]
     try:
-        if not ref.available():
-            pytest.skip("oracle/_ref/libsiftclref_sm.so not built (needs /root/reference)")
-        ref.PAR["DoubleImSize"] = 1
-        assert abs(ref.sigma_schedule()[0] - (1.6 ** 2 - 1.0) ** 0.5) < 1e-12
-        got = ref.keypoints(img)
+        pyref.PAR["DoubleImSize"] = 1
+        assert abs(pyref.sigma_schedule()[0] - (1.6 ** 2 - 1.0) ** 0.5) < 1e-12
     finally:
-        ref.PAR["DoubleImSize"] = saved
-        ref.use("glibc")
+        pyref.PAR["DoubleImSize"] = saved
     want = oracle.keypoints(img, par=oracle.default_params(double_im_size=1))
-    assert_same_keypoints(want, got, "DoubleImSize = 1")
+    assert_same_keypoints(want, ref[0]["double_im_size"], "DoubleImSize = 1")
     assert len(want) != len(oracle.keypoints(img))
 
 
 def test_converters_identical(ref):
     """The typed-frame GPU tests compare against `as_f32` (numpy casts, tests/test_gpu_typed_input.py); pin that
     restatement to the reference's converter kernels (preprocess.cl:53-223), values chosen so that (float)x rounds."""
-    rng = np.random.default_rng(12)
-    H, W = 37, 53
-    for name in ("uint8", "uint16", "uint32", "uint64", "int32", "int64"):
-        info = np.iinfo(name)
-        raw = rng.integers(info.min, info.max, (H, W), dtype=name, endpoint=True)
-        raw.flat[:4] = [info.min, info.max, 0, min(info.max, 2 ** 24 + 1)]      # extremes, and the first odd integer f32 cannot hold
-        assert np.array_equal(ref.to_float(raw).view(np.uint32), raw.astype(np.float32).view(np.uint32)), name
-    rgb = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    arrays = ref[0]
+    inputs = converter_inputs()
+    rgb = inputs.pop("rgb")
+    for name, raw in inputs.items():
+        assert np.array_equal(arrays["to_float_" + name].view(np.uint32), raw.astype(np.float32).view(np.uint32)), name
     r, g, b = (rgb[..., c].astype(np.float32) for c in range(3))
     want = (np.float32(0.299) * r + np.float32(0.587) * g) + np.float32(0.114) * b
-    assert np.array_equal(ref.to_float(rgb).view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(arrays["to_float_rgb"].view(np.uint32), want.view(np.uint32))
 
 
 def test_taps_identical_for_other_sigmas(oracle, ref):
-    for sigma in (0.8, 1.0, 2.2, 3.3, 5.0):
-        size = ref.kernel_size(sigma)
-        assert np.array_equal(oracle.gaussian_taps(sigma, size), ref.gaussian_taps(sigma, size))
+    from oracle import pyref
+    for i, sigma in enumerate(XCHECK_SIGMAS):
+        size = pyref.kernel_size(sigma)
+        assert np.array_equal(oracle.gaussian_taps(sigma, size), ref[0]["taps_%d" % i])
 
 
 def test_match_identical(oracle, ref):
-    img = smooth_noise((220, 220), seed=31)
-    k1 = oracle.keypoints(img)
-    k2 = oracle.keypoints(np.roll(img, (3, 4), axis=(0, 1)))
+    arrays = ref[0]
+    k1, k2 = arrays["match_k1"], arrays["match_k2"]
     p_o, n_o = oracle.match(k1, k2)
-    p_r, n_r = ref.match(k1, k2, cap=len(k1))
-    assert n_o == n_r and np.array_equal(sort_rows(p_o), sort_rows(p_r))
+    assert n_o == int(arrays["match_total"]) and np.array_equal(sort_rows(p_o), arrays["match_pairs"])
 
 
 def test_transform_identical(oracle, ref):
-    rng = np.random.default_rng(77)
-    img = (smooth_noise((150, 203), seed=78) * 1000.0 - 300.0).astype(np.float32)
-    rgb = rng.integers(0, 256, (64, 81, 3), dtype=np.uint8)
-    for k in range(12):
-        M = (np.eye(2) + rng.normal(0, 0.08, (2, 2))).astype(np.float32).reshape(4)
-        off = rng.normal(0, 12, 2).astype(np.float32)
-        fill = float(rng.integers(0, 200))
-        for mode in (1, 0):
-            a = oracle.transform(img, M, off, fill=fill, mode=mode); b = ref.transform(img, M, off, fill=fill, mode=mode)
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (k, mode)
-            assert np.array_equal(oracle.transform(rgb, M, off, fill=fill, mode=mode), ref.transform(rgb, M, off, fill=fill, mode=mode))
-        a = oracle.transform(img, M, off, out_shape=(180, 230), fill=fill); b = ref.transform(img, M, off, out_shape=(180, 230), fill=fill)
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    digests = ref[1]["transform"]
+    cases = transform_xcheck_cases()
+    assert len(cases) == len(digests) == 12 * 5
+    for name, img, M, off, out_shape, fill, mode in cases:
+        assert array_digest(oracle.transform(img, M, off, out_shape=out_shape, fill=fill, mode=mode)) == digests[name], name
 
 
 def test_matching_valid_identical(oracle, ref):
     """so_match_ex(roi_mode=1) against the reference's `matching_valid` kernel (never launched by its host code)."""
-    from util import dtype_kp
-    rng = np.random.default_rng(5)
-    n1, n2, H, W = 600, 550, 90, 120
-    a = np.zeros(n1, dtype_kp); b = np.zeros(n2, dtype_kp)
-    a["desc"] = rng.integers(0, 256, (n1, 128), dtype=np.uint8); b["desc"] = rng.integers(0, 256, (n2, 128), dtype=np.uint8)
-    idx = rng.permutation(n1)[:300]
-    b["desc"][:300] = np.clip(a["desc"][idx].astype(int) + rng.integers(-6, 7, (300, 128)), 0, 255).astype(np.uint8)
-    roi = (rng.random((H, W)) > 0.3).astype(np.int8)
-    ys, xs = np.nonzero(roi)
-    pick = rng.integers(0, len(ys), n2)
-    b["x"] = xs[pick] + 0.4; b["y"] = ys[pick] + 0.6                  # list 2 entirely on valid pixels
-    a["x"] = rng.random(n1) * W * 1.2; a["y"] = rng.random(n1) * H * 1.2   # list 1 anywhere, also beyond the array
-    p_o, n_o = oracle.match_ex(a, b, roi, 1); p_r, n_r = ref.match_valid(a, b, roi)
-    assert n_o == n_r and 0 < n_o < 300 and np.array_equal(sort_rows(p_o), sort_rows(p_r))
+    arrays = ref[0]
+    a, b, roi = matching_valid_inputs()
+    got = {}
+    for label, bs in matching_valid_steps(b, roi):
+        p_o, n_o = oracle.match_ex(a, bs, roi, 1)
+        assert n_o == int(arrays["valid_%s_total" % label]), label
+        assert np.array_equal(sort_rows(p_o), arrays["valid_%s_pairs" % label]), label
+        got[label] = (p_o, n_o)
+    p_o, n_o = got["plain"]
+    assert 0 < n_o < 300
     # one masked-out list-2 keypoint wins everything; two of them suppress every pair
-    zy, zx = np.argwhere(roi == 0)[0]
-    b["x"][7] = zx + 0.5; b["y"][7] = zy + 0.5
-    p_o, n_o = oracle.match_ex(a, b, roi, 1); p_r, n_r = ref.match_valid(a, b, roi)
-    assert n_o == n_r and n_o > 300 and np.array_equal(sort_rows(p_o), sort_rows(p_r)) and (p_o[:, 1] == 7).all()
-    b["x"][8] = zx + 0.5; b["y"][8] = zy + 0.5
-    assert oracle.match_ex(a, b, roi, 1)[1] == 0 == ref.match_valid(a, b, roi)[1]
+    p_o, n_o = got["one_masked"]
+    assert n_o > 300 and (p_o[:, 1] == 7).all()
+    assert got["two_masked"][1] == 0
     # list-2 keypoints beyond the array also count as masked out
-    b["x"][8] = W + 3.0
-    assert oracle.match_ex(a, b, roi, 1)[1] == 0 == ref.match_valid(a, b, roi)[1]
+    assert got["one_beyond"][1] == 0

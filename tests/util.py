@@ -169,3 +169,85 @@ def transform_inputs():
     gray = (smooth_noise((97, 131), seed=41, sigma=1.5) * 255.0).astype(np.float32)
     rgb = np.random.default_rng(42).integers(0, 256, (40, 53, 3), dtype=np.uint8)
     return gray, rgb
+
+
+# ---- inputs of tests/test_oracle_vs_ref.py, shared with the generator of its fixture (tests/golden/make_ref_xcheck.py)
+PIPELINE_CASES = [(21, (200, 333), True), (22, (160, 160), False), (23, (97, 211), True)]
+XCHECK_SIGMAS = (0.8, 1.0, 2.2, 3.3, 5.0)
+
+
+def pipeline_input(seed, shape, smooth):
+    return smooth_noise(shape, seed=seed, sigma=2.5) if smooth else white_noise(shape, seed=seed)
+
+
+def converter_inputs():
+    """{dtype name: raw frame} of integer frames whose extremes and (float)x roundings the converters must reproduce,
+    plus "rgb": an RGB uint8 frame."""
+    rng = np.random.default_rng(12)
+    H, W = 37, 53
+    out = {}
+    for name in ("uint8", "uint16", "uint32", "uint64", "int32", "int64"):
+        info = np.iinfo(name)
+        raw = rng.integers(info.min, info.max, (H, W), dtype=name, endpoint=True)
+        raw.flat[:4] = [info.min, info.max, 0, min(info.max, 2 ** 24 + 1)]      # extremes, and the first odd integer f32 cannot hold
+        out[name] = raw
+    out["rgb"] = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    return out
+
+
+def transform_xcheck_cases():
+    """[(name, image, matrix, offset, out_shape, fill, mode)]: twelve random affine warps of a float and an RGB image,
+    both interpolation modes, plus a larger output shape."""
+    rng = np.random.default_rng(77)
+    img = (smooth_noise((150, 203), seed=78) * 1000.0 - 300.0).astype(np.float32)
+    rgb = rng.integers(0, 256, (64, 81, 3), dtype=np.uint8)
+    cases = []
+    for k in range(12):
+        M = (np.eye(2) + rng.normal(0, 0.08, (2, 2))).astype(np.float32).reshape(4)
+        off = rng.normal(0, 12, 2).astype(np.float32)
+        fill = float(rng.integers(0, 200))
+        for mode in (1, 0):
+            cases.append(("gray%d_mode%d" % (k, mode), img, M, off, None, fill, mode))
+            cases.append(("rgb%d_mode%d" % (k, mode), rgb, M, off, None, fill, mode))
+        cases.append(("gray%d_out180x230" % k, img, M, off, (180, 230), fill, 1))
+    return cases
+
+
+def matching_valid_inputs():
+    """(a, b, roi): list 2 entirely on valid pixels of a random mask, list 1 anywhere, also beyond the array; 300 of
+    list 2 are perturbed copies of list 1."""
+    rng = np.random.default_rng(5)
+    n1, n2, H, W = 600, 550, 90, 120
+    a = np.zeros(n1, dtype_kp); b = np.zeros(n2, dtype_kp)
+    a["desc"] = rng.integers(0, 256, (n1, 128), dtype=np.uint8); b["desc"] = rng.integers(0, 256, (n2, 128), dtype=np.uint8)
+    idx = rng.permutation(n1)[:300]
+    b["desc"][:300] = np.clip(a["desc"][idx].astype(int) + rng.integers(-6, 7, (300, 128)), 0, 255).astype(np.uint8)
+    roi = (rng.random((H, W)) > 0.3).astype(np.int8)
+    ys, xs = np.nonzero(roi)
+    pick = rng.integers(0, len(ys), n2)
+    b["x"] = xs[pick] + 0.4; b["y"] = ys[pick] + 0.6
+    a["x"] = rng.random(n1) * W * 1.2; a["y"] = rng.random(n1) * H * 1.2
+    return a, b, roi
+
+
+def matching_valid_steps(b, roi):
+    """The list-2 variants matched in turn, as (label, b): as generated; one masked-out list-2 keypoint; two of them;
+    the second one moved beyond the array instead."""
+    W = roi.shape[1]
+    zy, zx = np.argwhere(roi == 0)[0]
+    steps = [("plain", b.copy())]
+    b = b.copy()
+    b["x"][7] = zx + 0.5; b["y"][7] = zy + 0.5
+    steps.append(("one_masked", b.copy()))
+    b["x"][8] = zx + 0.5; b["y"][8] = zy + 0.5
+    steps.append(("two_masked", b.copy()))
+    b["x"][8] = W + 3.0
+    steps.append(("one_beyond", b.copy()))
+    return steps
+
+
+def array_digest(a):
+    """SHA-256 of an array's dtype, shape and bytes."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(("%s %s|" % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()

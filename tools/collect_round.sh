@@ -34,7 +34,7 @@ for leg in c3 c4; do f=$(ls $OUT/kt_$leg/*/*kernel_stats.csv $OUT/kt_$leg/*kerne
 bash tools/collect_c3_traffic.sh $TAG > $OUT/collect_c3.log 2>&1
 cp gpurun_out/prof_c3_$TAG/blur_traffic.json $OUT/blur_traffic_c3.json 2>/dev/null
 cp gpurun_out/prof_c3_$TAG/summary.txt $OUT/rocprofv3_summary_c3.txt 2>/dev/null
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 ls -la $OUT
 # keep what travels back small (gpurun merges at most 64 MiB): the raw CSVs stay on the box
 rm -rf gpurun_out/prof_$TAG gpurun_out/pmc_* gpurun_out/trace_gaps

@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev (round 3): baseline + descriptor ablation + FP64 instruction split on one box
 R=$(pwd); OUT=$R/gpurun_out/r3b1; rm -rf $OUT; mkdir -p $OUT
-python bench.py --no-cpu-baseline > $OUT/bench_base.json 2> $OUT/bench_base.err
+python bench.py --full --no-cpu-baseline > $OUT/bench_base.json 2> $OUT/bench_base.err
 (cd /tmp && rocprofv3 -L > $OUT/counters.txt 2>&1)
 grep -o "SQ_INSTS_VALU[A-Z0-9_]*" $OUT/counters.txt | sort -u > $OUT/valu_counters.txt
 # ablation build of the library
@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64" "SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32" "SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT" "SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAVES" "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --kernel-trace -d $OUT/pmc/g$i -o pmc --output-format csv -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_g$i.err
+  rocprofv3 --pmc $grp --kernel-trace -d $OUT/pmc/g$i -o pmc --output-format csv -- python $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_g$i.err
 done
 cd $R
 python - <<'PY' > $OUT/pmc_fp64.txt 2>&1
