@@ -91,15 +91,25 @@ int so_gaussian_taps(float sigma, int size, float *out) {
 }
 
 /* ------------------------------------------------------------------ A2: min/max + normalise
- * reductions.cl:217-241 (serial variant; min/max are order independent so the two-stage
- * variant gives the same bits), preprocess.cl:239-252. */
+ * max_min_global_stage1/2 (reductions.cl:62-199), the path plan.py:490-522 takes by default, and preprocess.cl:239-252.
+ * The two-stage kernels reduce with fmax / fmin (REDUCE, reductions.cl:44): a NaN pixel is ignored, and only an all-NaN
+ * frame gives NaN.  Any reduction order gives those bits.  (The serial fallback max_min_serial, reductions.cl:217-241,
+ * agrees on frames without NaN; from a NaN at pixel 0 it would return NaN.) */
 void so_minmax(const float *img, int64_t n, float *mn, float *mx) {
-    float lo = img[0], hi = img[0];
-#pragma omp parallel for reduction(min : lo) reduction(max : hi) schedule(static)
-    for (int64_t i = 1; i < n; i++) {
-        float v = img[i];
-        if (v > hi) hi = v;
-        if (v < lo) lo = v;
+    float lo = NAN, hi = NAN;                 /* fminf(NaN, v) = v: the identity of the NaN-ignoring reduction */
+#pragma omp parallel
+    {
+        float tlo = NAN, thi = NAN;
+#pragma omp for schedule(static) nowait
+        for (int64_t i = 0; i < n; i++) {
+            tlo = fminf(tlo, img[i]);
+            thi = fmaxf(thi, img[i]);
+        }
+#pragma omp critical
+        {
+            lo = fminf(lo, tlo);
+            hi = fmaxf(hi, thi);
+        }
     }
     *mn = lo; *mx = hi;
 }

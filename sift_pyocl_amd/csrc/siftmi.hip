@@ -98,6 +98,10 @@ int kernel_size(double sigma) {   // utils.py:54-64 with odd=True, cutoff=4
 
 struct Taps { int n = 0; float t[64] = {0}; float *dev = nullptr; };
 
+// Largest "ori_pad" / "desc_pad" (bytes of dynamic LDS added to each workgroup of the orientation / descriptor launch): with
+// the kernels' static LDS (12.5 KiB / 34 KiB) a workgroup still fits the 160 KiB of a CU; a larger pad would fail the launch.
+#define SIFT_LDS_PAD_MAX 65536
+
 // Per-plan tuning / diagnostic options (siftmi_plan_set_option).  Defaults are the measured best; nothing on the launch
 // path reads the environment.
 struct Options {
@@ -993,6 +997,7 @@ int siftmi_plan_set_params(siftmi_plan *p, const siftmi_params *params) {
 int siftmi_plan_set_option(siftmi_plan *p, const char *name, int64_t value) {
     if (!p || !name) return fail(SIFTMI_EINVAL, "null argument");
     const std::string n(name);
+    if (value < INT32_MIN || value > INT32_MAX) return fail(SIFTMI_EINVAL, "option '%s': value %lld is outside int32", name, (long long)value);
     const int v = (int)value;
     Options &o = p->opt;
     if (n == "fused_convert") o.fused_convert = v != 0;
@@ -1002,9 +1007,9 @@ int siftmi_plan_set_option(siftmi_plan *p, const char *name, int64_t value) {
     else if (n == "xcd_map") o.xcd_map = v != 0;
     else if (n == "march_prio") { if (v < 0 || v > 2) return fail(SIFTMI_EINVAL, "march_prio must be 0, 1 or 2"); o.march_prio = (int)v; }
     else if (n == "ori_blocks") { if (v < 1) return fail(SIFTMI_EINVAL, "ori_blocks must be >= 1"); o.ori_blocks = v; }
-    else if (n == "ori_pad") o.ori_pad = v > 0 ? v : 0;
+    else if (n == "ori_pad") { if (v < 0 || v > SIFT_LDS_PAD_MAX) return fail(SIFTMI_EINVAL, "ori_pad must be in 0..%d", SIFT_LDS_PAD_MAX); o.ori_pad = v; }
     else if (n == "desc_blocks") { if (v < 1) return fail(SIFTMI_EINVAL, "desc_blocks must be >= 1"); o.desc_blocks = v; }
-    else if (n == "desc_pad") o.desc_pad = v;
+    else if (n == "desc_pad") { if (v < 0 || v > SIFT_LDS_PAD_MAX) return fail(SIFTMI_EINVAL, "desc_pad must be in 0..%d", SIFT_LDS_PAD_MAX); o.desc_pad = v; }
     else if (n == "desc_stream") o.desc_stream = v != 0;
     else if (n == "mm_threads") { if (v != 256 && v != 512 && v != 1024) return fail(SIFTMI_EINVAL, "mm_threads must be 256, 512 or 1024"); o.mm_threads = v; }
     else if (n == "mm_blocks") { if (v < 1) return fail(SIFTMI_EINVAL, "mm_blocks must be >= 1"); o.mm_blocks = v; }
