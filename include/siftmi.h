@@ -253,8 +253,10 @@ int siftmi_stage_blur(int32_t device_id, const float *in, float *out, int32_t W,
  * `in_dtype` (SIFTMI_F32, or an integer / RGB8 code: those enter through the normalising 15-tap blur only, as in a plan);
  * norm != 0: min/max of the frame first (reductions.cl:62-241), then the blur with `normalizes` (preprocess.cl:239-252)
  * applied to its inputs; xcd_map: bit 0 = workgroup order of the marching kernel (option "xcd_map"), bit 1 set = its priority
- * feedback off (option "march_prio" 0); march_wgs: its workgroup count (0: default);
- * *kernel_used (may be null): 0 generic two-pass, 1 tiled kernel, 2 marching team kernel. */
+ * feedback off (option "march_prio" 0), bits 2-3 = the small-plane blur form plus one (0: the default rule, 1: 32 x 16 tile kernel,
+ * 2: 32 x 32 / 32 x 64 tile kernel, 3: by plane size); march_wgs: its workgroup count (0: default);
+ * *kernel_used (may be null): 0 generic two-pass, 1 tiled kernel, 2 marching team kernel, 3 32 x 32 / 32 x 64 tile kernel -- the kernel
+ * that was launched. */
 int siftmi_stage_blur_ex(int32_t device_id, const void *in, int32_t in_dtype, float *out, int32_t W, int32_t H,
                          const float *taps, int32_t ntaps, int32_t norm, int32_t xcd_map, int32_t march_wgs,
                          int32_t *kernel_used);

@@ -664,6 +664,146 @@ __global__ __launch_bounds__(64 * HW + 128) void blur_team_kernel(const void *__
 }
 
 
+// ------------------------------------------------------------------------------------------
+// Tile blur, second form, for planes below the marching cross-over with bitwise-symmetric odd tap lists.
+//
+// One segment of L outputs along a line (a row pair in the H pass, a column pair in the V pass), two lines packed in the two
+// halves of f32x2: the L + N - 1 inputs arrive in ascending order (rd(i)), input i forms each product x * taps[k] once
+// (k = 0 .. (N-1)/2) and adds it to the outputs ya = i - k and yb = i - (N-1-k) that lie in the segment.  Output y receives
+// input i at q = i - y with taps[N-1-q], which is bitwise taps[k] for either k, so every output gets the reference's
+// products in the reference's order (q ascending, starting from 0.0f).  All indices are compile-time constants.
+template <int N, int L, class RD> __device__ __forceinline__ void blur_segment(const float (&t)[N], RD rd, f32x2 (&acc)[L]) {
+#pragma unroll
+    for (int j = 0; j < L; j++) acc[j] = (f32x2){0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < L + N - 1; i++) {
+        const f32x2 x = rd(i);
+#pragma unroll
+        for (int k = 0; k <= (N - 1) / 2; k++) {
+            const int ya = i - k, yb = i - (N - 1 - k);
+            const bool na = ya >= 0 && ya < L, nb = k != N - 1 - k && yb >= 0 && yb < L;
+            if (!na && !nb) continue;
+            const f32x2 p = x * (f32x2){t[k], t[k]};
+            if (na) acc[ya] = acc[ya] + p;
+            if (nb) acc[yb] = acc[yb] + p;
+        }
+    }
+}
+
+// TX x TY tile, 256 threads, LDS window of (TY+N-1) x (TX+N-1) with the rows interleaved in pairs ([row pair][col][row&1]):
+//   1. staging: a wave stages one row pair per step (two rows of one column per lane, 8-byte LDS stores); the source
+//      columns are computed once per thread and the rows are wave-uniform, so an interior tile adds a row pitch per step
+//      and only border tiles reflect (the row in a scalar register),
+//   2. horizontal pass in place: a lane owns L = 8 outputs of a row pair (blur_segment, packed over the two rows) and
+//      writes them as [row pair][col pair][row][2 cols], all lanes of a row pair in one wave,
+//   3. vertical pass: a lane owns one column pair and VR = 8 output rows (blur_segment over VR + N - 1 rows, 16-byte reads).
+// Same outputs, NORM, typed loads and fused hand-off as blur_hv_kernel.
+template <int N, int TX, int TY> struct Tile2Geom {
+    static constexpr int C = N / 2;
+    static constexpr int L = 8, VR = 8;
+    static constexpr int ROWS = TY + N - 1, RP = ROWS / 2;
+    static constexpr int COLS = TX + N - 1;
+    static constexpr int PITCH = (COLS + 1) & ~1;            // in row-pair columns (f32x2): even keeps the 16-byte reads aligned
+    static constexpr int LDS_BYTES = RP * PITCH * 8;
+};
+
+template <int N, bool NORM, int DT = 0, int TX = 32, int TY = 64>
+__global__ __launch_bounds__(256) void blur_tile2_kernel(const void *__restrict__ in, float *__restrict__ out,
+                                                         int W, int H, TapsArg<N> taps,
+                                                         const uint32_t *__restrict__ mm,
+                                                         float *__restrict__ half) {   // not null: also out[2y][2x] -> half
+    using G = Tile2Geom<N, TX, TY>;
+    static_assert(N & 1, "odd tap counts only");
+    static_assert(TY % G::VR == 0 && TX % G::L == 0 && 64 % (TX / G::L) == 0 && G::COLS <= 128, "tile shape");
+    extern __shared__ float4 smem4[];
+    float *s = reinterpret_cast<float *>(smem4);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+
+    float mn = 0.f, range = 1.f;
+    if (NORM) { mn = ord2f(mm[0]); range = ord2f(mm[1]) - mn; }
+
+    // ---- 1. stage the window: wave w stages row pairs w, w + 4, ...; lane owns columns lane and lane + 64
+    {
+        const int c1 = lane + 64;
+        const bool has0 = lane < G::COLS, has1 = c1 < G::COLS;
+        const int gxa = reflect_index(x0 - G::C + lane, W), gxb = reflect_index(x0 - G::C + (has1 ? c1 : lane), W);
+        const int ytop = y0 - G::C;
+        const bool inside = ytop >= 0 && ytop + G::ROWS <= H;     // workgroup uniform
+        auto fetch = [&](int gy, int gx) {
+            float v = load_px<DT>(in, (size_t)gy * W + gx);
+            if (NORM) v = 255.0f * (v - mn) / range;     // preprocess.cl:250
+            return v;
+        };
+        f32x2 *s2 = reinterpret_cast<f32x2 *>(s);
+        if (inside) {
+#pragma unroll 2
+            for (int rp = wave; rp < G::RP; rp += 4) {
+                const int gy = ytop + 2 * rp;
+                if (has0) s2[rp * G::PITCH + lane] = (f32x2){fetch(gy, gxa), fetch(gy + 1, gxa)};
+                if (has1) s2[rp * G::PITCH + c1] = (f32x2){fetch(gy, gxb), fetch(gy + 1, gxb)};
+            }
+        } else {
+#pragma unroll 2
+            for (int rp = wave; rp < G::RP; rp += 4) {
+                const int gy0 = reflect_index(ytop + 2 * rp, H), gy1 = reflect_index(ytop + 2 * rp + 1, H);
+                if (has0) s2[rp * G::PITCH + lane] = (f32x2){fetch(gy0, gxa), fetch(gy1, gxa)};
+                if (has1) s2[rp * G::PITCH + c1] = (f32x2){fetch(gy0, gxb), fetch(gy1, gxb)};
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. horizontal pass, in place: task = (row pair, L outputs)
+    constexpr int HT = TX / G::L;
+    for (int task = tid; task < G::RP * HT; task += 256) {
+        const int rp = task / HT, c0 = (task - rp * HT) * G::L;
+        float *rowp = s + (rp * G::PITCH + c0) * 2;
+        f32x2 acc[G::L];
+        blur_segment<N, G::L>(taps.t, [&](int i) { return *reinterpret_cast<const f32x2 *>(rowp + 2 * i); }, acc);
+        // All tasks of a row pair sit in one wave and LDS executes a wave's operations in order: every lane has issued its
+        // reads before any lane stores.  Keep the compiler from moving the stores up.
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < G::L; j += 2)
+            *reinterpret_cast<f32x4 *>(rowp + 2 * j) = (f32x4){acc[j].x, acc[j + 1].x, acc[j].y, acc[j + 1].y};
+    }
+    __syncthreads();
+
+    // ---- 3. vertical pass: task = (column pair, VR rows)
+    constexpr int CP = TX / 2;
+    for (int task = tid; task < CP * (TY / G::VR); task += 256) {
+        const int rg = task / CP, c = (task - rg * CP) * 2;
+        const int r0 = rg * G::VR;
+        const float *colp = s + ((r0 / 2) * G::PITCH + c) * 2;
+        f32x4 v;
+        f32x2 acc[G::VR];
+        blur_segment<N, G::VR>(taps.t, [&](int i) {
+            if (!(i & 1)) v = *reinterpret_cast<const f32x4 *>(colp + (i / 2) * G::PITCH * 2);
+            return (i & 1) ? v.zw : v.xy;
+        }, acc);
+        const int gx = x0 + c;
+        const bool vec = ((W & 1) == 0) && gx + 1 < W;
+#pragma unroll
+        for (int j = 0; j < G::VR; j++) {
+            const int gy = y0 + r0 + j;
+            if (gy < H) {
+                float *o = out + (size_t)gy * W + gx;
+                if (vec) *reinterpret_cast<f32x2 *>(o) = acc[j];
+                else {
+                    if (gx < W) o[0] = acc[j].x;
+                    if (gx + 1 < W) o[1] = acc[j].y;
+                }
+                // octave hand-off (preprocess.cl:267-285) fused into the launch that writes plane 3 (gx is even)
+                if (half && !(gy & 1) && (gy >> 1) < (H >> 1) && (gx >> 1) < (W >> 1))
+                    half[(size_t)(gy >> 1) * (W >> 1) + (gx >> 1)] = acc[j].x;
+            }
+        }
+    }
+}
+
+
 // Generic (any tap count, incl. even sizes) two-pass blur: plain global loads, used only for
 // non-default init_sigma schedules and stage replay.  Same arithmetic.
 __global__ void blur_generic_pass(const float *__restrict__ in, float *__restrict__ out, int W, int H,

@@ -108,6 +108,8 @@ struct Options {
     int fused_convert = 1;   // typed frames converted at the point of use (0: separate convert pass)
     int overlap = 1;         // detection / description streams beside the pyramid stream (0: one stream)
     int march = 1;           // marching blur for large planes (0: tiled blur everywhere)
+    int small_blur = 2;      // planes below the marching cross-over with symmetric odd taps: 0 the 32 x 16 tile kernel (blur_hv_kernel),
+                             // 1 the 32 x 32 / 32 x 64 tile kernel (blur_tile2_kernel), 2 by plane size (tile2_plane)
     int march_wgs = 0;       // workgroups wanted by the marching blur (0: 1024, 768 for 27 taps)
     int xcd_map = 1;         // marching blur: whole segment rows per XCD (k_pyramid.hpp: the strips' halo columns become L2 hits)
     int march_prio = 1;      // marching blur: wave priority falls by one level per quarter of a workgroup's march, so that the workgroups of a CU
@@ -343,15 +345,43 @@ void launch_blur_geom(hipStream_t st, const void *in, float *out, int W, int H, 
     launch_ev(stop, blur_hv_kernel<N, NORM, DT, TX, TY, VR>, grid, dim3(256), (size_t)G::LDS_BYTES, st, in, out, W, H, ta, mm, half);
 }
 
+template <int N, bool NORM, int DT, int TX, int TY>
+void launch_tile2(hipStream_t st, const void *in, float *out, int W, int H, const TapsArg<N> &ta, const uint32_t *mm, float *half, hipEvent_t stop) {
+    using G = Tile2Geom<N, TX, TY>;
+    dim3 grid((unsigned)((W + TX - 1) / TX), (unsigned)((H + TY - 1) / TY));
+    launch_ev(stop, blur_tile2_kernel<N, NORM, DT, TX, TY>, grid, dim3(256), (size_t)G::LDS_BYTES, st, in, out, W, H, ta, mm, half);
+}
+
+// Which kernel ran a blur (the stage entry point reports it): none (no fused instance for the tap count), the 32 x 16 tile
+// kernel, the marching team kernel, the small-plane tile kernel (blur_tile2_kernel).
+enum BlurForm { BLUR_NONE = 0, BLUR_TILE = 1, BLUR_TEAM = 2, BLUR_TILE2 = 3 };
+
+// blur_tile2_kernel takes a plane (below the marching cross-over) when its taps are bitwise symmetric and
+// Options::small_blur asks for it: 1 always, 2 from TILE2_MIN_PIXELS on.  32 x 64 tiles from TILE2_TALL_PIXELS on, 32 x 32 below.
+// Alone (tools/ubench/blur_tile2.hip, 11 / 15 / 17 / 21 / 27 taps) against the 32 x 16 tile kernel: 1024^2 32 x 64 6.1 / 6.5 / 6.8 /
+// 7.5 / 8.2 us against 7.1 / 8.4 / 8.8 / 11.1 / 15.6 (64 x 64: 256 workgroups, 7.4 - 10.0); 600^2 32 x 32 4.8 / 5.1 / 5.4 / 5.9 / 6.7
+// against 4.7 / 5.4 / 5.7 / 6.8 / 8.4; 512^2 a tie up to 17 taps, and whole 512^2 frames measured no faster: they keep the old kernel.
+constexpr int64_t TILE2_MIN_PIXELS = 600 * 600;
+constexpr int64_t TILE2_TALL_PIXELS = 1024 * 1024;
+inline bool tile2_plane(const Options &opt, int W, int H, bool symmetric) {
+    return symmetric && (opt.small_blur == 1 || (opt.small_blur == 2 && (int64_t)W * H >= TILE2_MIN_PIXELS));
+}
+
 // Tile shape: planes that reach this kernel are narrower than 1024 columns or shorter than 512 rows (larger ones take the
 // marching kernel); on all of them the 32 x 16 tile measured fastest (whole call, MI355X, round 2: 512^2 0.75 / 0.52 / 0.44 ms
 // and 1020^2 0.90 / 0.63 / 0.53 ms for 128x64 / 64x32 / 32x16 tiles).
 template <int N, bool NORM, int DT = 0>
-void launch_blur_t(const Options &opt, hipStream_t st, const void *in, float *out, int W, int H, const float *taps, const uint32_t *mm, float *half = nullptr, hipEvent_t stop = nullptr) {
+BlurForm launch_blur_t(const Options &opt, hipStream_t st, const void *in, float *out, int W, int H, const float *taps, bool symmetric,
+                       const uint32_t *mm, float *half = nullptr, hipEvent_t stop = nullptr) {
     TapsArg<N> ta;
     for (int i = 0; i < N; i++) ta.t[i] = taps[i];
-    (void)opt;
+    if (tile2_plane(opt, W, H, symmetric)) {
+        if ((int64_t)W * H >= TILE2_TALL_PIXELS) launch_tile2<N, NORM, DT, 32, 64>(st, in, out, W, H, ta, mm, half, stop);
+        else launch_tile2<N, NORM, DT, 32, 32>(st, in, out, W, H, ta, mm, half, stop);
+        return BLUR_TILE2;
+    }
     launch_blur_geom<N, NORM, DT, 32, 16, 4>(st, in, out, W, H, ta, mm, half, stop);
+    return BLUR_TILE;
 }
 
 // team form of the marching blur (blur_team_kernel): S sub-blocks per accumulator period, `wgs` workgroups wanted.
@@ -401,40 +431,45 @@ bool launch_march_t(const Options &opt, hipStream_t st, const void *in, float *o
     return half != nullptr;
 }
 
-// returns 0 when no tiled instantiation exists for this tap count, 1 when launched, 2 when launched and `half` written
 // The marching kernels amortise their prologue over long strips; measured cross-over with the 32 x 16 tile kernel
 // is near 1400^2 (whole call 0.607 vs 0.609 ms; 1024^2 0.555 vs 0.529, 2048^2 0.732 vs 0.779).
 inline bool march_plane(int W, int H) { return W >= 1024 && H >= 512 && (int64_t)W * H >= 1400 * 1400; }
 
-template <bool NORM>
-int launch_blur_tiled(const Options &opt, hipStream_t st, const float *in, float *out, int W, int H, const Taps &t, const uint32_t *mm, float *half = nullptr, hipEvent_t stop = nullptr) {
+bool taps_symmetric(const Taps &t) {
     bool symmetric = true;
     for (int i = 0; i < t.n / 2; i++) symmetric = symmetric && (memcmp(&t.t[i], &t.t[t.n - 1 - i], 4) == 0);
+    return symmetric;
+}
+
+// returns the kernel launched (BlurForm; BLUR_NONE when no fused instantiation exists for this tap count).  Every fused form
+// writes `half` when it is not null.
+template <bool NORM>
+BlurForm launch_blur_tiled(const Options &opt, hipStream_t st, const float *in, float *out, int W, int H, const Taps &t, const uint32_t *mm, float *half = nullptr, hipEvent_t stop = nullptr) {
+    const bool symmetric = taps_symmetric(t);
     if constexpr (NORM) {
         // The normalising form exists for the default initial kernel only (15 taps, init_sigma = 1.6); any other
-        // InitSigma sends its ONE initial blur through the generic two-pass path (return 0).
-        if (t.n != 15) return 0;
-        if (march_plane(W, H) && symmetric && opt.march) return launch_march_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop) ? 2 : 1;
-        launch_blur_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop);
-        return half ? 2 : 1;
+        // InitSigma sends its ONE initial blur through the generic two-pass path (BLUR_NONE).
+        if (t.n != 15) return BLUR_NONE;
+        if (march_plane(W, H) && symmetric && opt.march) { launch_march_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM; }
+        return launch_blur_t<15, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
     } else {
     if (march_plane(W, H) && symmetric && opt.march) {
         switch (t.n) {
-            case 11: return launch_march_t<11, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop) ? 2 : 1;
-            case 15: return launch_march_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop) ? 2 : 1;
-            case 17: return launch_march_t<17, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop) ? 2 : 1;
-            case 21: return launch_march_t<21, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop) ? 2 : 1;
-            case 27: return launch_march_t<27, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop) ? 2 : 1;
+            case 11: launch_march_t<11, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
+            case 15: launch_march_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
+            case 17: launch_march_t<17, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
+            case 21: launch_march_t<21, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
+            case 27: launch_march_t<27, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
             default: break;
         }
     }
     switch (t.n) {
-        case 11: launch_blur_t<11, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return half ? 2 : 1;
-        case 15: launch_blur_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return half ? 2 : 1;
-        case 17: launch_blur_t<17, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return half ? 2 : 1;
-        case 21: launch_blur_t<21, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return half ? 2 : 1;
-        case 27: launch_blur_t<27, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return half ? 2 : 1;
-        default: return 0;
+        case 11: return launch_blur_t<11, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+        case 15: return launch_blur_t<15, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+        case 17: return launch_blur_t<17, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+        case 21: return launch_blur_t<21, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+        case 27: return launch_blur_t<27, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+        default: return BLUR_NONE;
     }
     }
 }
@@ -453,32 +488,24 @@ bool launch_blur(siftmi_plan *p, const float *in, float *out, int W, int H, cons
     if (!st) st = p->stream;
     Options opt = p->opt;
     if (opt.march_prio == 1 && st != p->stream) opt.march_prio = 2;      // a later octave's chain (launch_team)
-    const int r = norm ? launch_blur_tiled<true>(opt, st, in, out, W, H, t, p->mm, half, stop)
-                       : launch_blur_tiled<false>(opt, st, in, out, W, H, t, p->mm, half, stop);
-    if (!r) {       // one intermediate plane per stream that builds pyramids: the chains run beside one another
+    const BlurForm r = norm ? launch_blur_tiled<true>(opt, st, in, out, W, H, t, p->mm, half, stop)
+                            : launch_blur_tiled<false>(opt, st, in, out, W, H, t, p->mm, half, stop);
+    if (r == BLUR_NONE) {       // one intermediate plane per stream that builds pyramids: the chains run beside one another
         float *tmp = (st == p->stream2 && p->tmp_below) ? p->tmp_below : ((st == p->stream3 && p->tmp_later) ? p->tmp_later : p->tmp);
         launch_blur_generic(st, in, out, tmp, W, H, t, p->mm, norm);
         if (stop) (void)hipEventRecord(stop, st);
     }
-    return r == 2;
-}
-
-bool taps_symmetric(const Taps &t) {
-    bool symmetric = true;
-    for (int i = 0; i < t.n / 2; i++) symmetric = symmetric && (memcmp(&t.t[i], &t.t[t.n - 1 - i], 4) == 0);
-    return symmetric;
+    return r != BLUR_NONE && half;
 }
 
 // Initial blur reading a typed (integer / RGB) frame directly: instantiated for the default 15-tap initial
 // kernel (init_sigma = 1.6); any other tap count goes through the convert pass.
 template <int DT>
-bool launch_init_blur_dt(const Options &opt, hipStream_t st, const void *in, float *out, int W, int H, const Taps &t, const uint32_t *mm) {
-    if (t.n != 15) return false;
-    if (march_plane(W, H) && taps_symmetric(t) && opt.march)
-        launch_march_t<15, true, DT>(opt, st, in, out, W, H, t.t, mm);
-    else
-        launch_blur_t<15, true, DT>(opt, st, in, out, W, H, t.t, mm);
-    return true;
+BlurForm launch_init_blur_dt(const Options &opt, hipStream_t st, const void *in, float *out, int W, int H, const Taps &t, const uint32_t *mm) {
+    if (t.n != 15) return BLUR_NONE;
+    const bool symmetric = taps_symmetric(t);
+    if (march_plane(W, H) && symmetric && opt.march) { launch_march_t<15, true, DT>(opt, st, in, out, W, H, t.t, mm); return BLUR_TEAM; }
+    return launch_blur_t<15, true, DT>(opt, st, in, out, W, H, t.t, symmetric, mm);
 }
 
 // dispatch F(DT) over the typed-frame codes that have a fused path
@@ -2453,6 +2480,7 @@ int siftmi_stage_blur_ex(int32_t dev, const void *in, int32_t in_dtype, float *o
     opt.xcd_map = (xcd_map & 1) ? 1 : 0;
     opt.march_prio = (xcd_map & 2) ? 0 : 2;       // (forced where not off: the stage planes are smaller than the rule's)
     opt.march_wgs = march_wgs > 0 ? march_wgs : 0;
+    if ((xcd_map >> 2) & 3) opt.small_blur = ((xcd_map >> 2) & 3) - 1;
     uint32_t *mmp = mm.as<uint32_t>();
     if (norm) {
         hipLaunchKernelGGL(minmax_init, dim3(1), dim3(1), 0, 0, mmp);
@@ -2463,21 +2491,14 @@ int siftmi_stage_blur_ex(int32_t dev, const void *in, int32_t in_dtype, float *o
                                                                (const void *)a.p, (int64_t)N, mmp));
         }
     }
-    int used = 0;
+    BlurForm used = BLUR_NONE;
     if (in_dtype != SIFTMI_F32) {
-        bool ok = false;
-        SIFTMI_TYPED_DISPATCH(in_dtype, ok = launch_init_blur_dt<DT>(opt, 0, (const void *)a.p, b.as<float>(), W, H, tp, mmp));
-        if (!ok) return fail(SIFTMI_EINVAL, "no fused blur for input format %d", in_dtype);
-        used = (march_plane(W, H) && taps_symmetric(tp) && opt.march) ? 2 : 1;
+        SIFTMI_TYPED_DISPATCH(in_dtype, used = launch_init_blur_dt<DT>(opt, 0, (const void *)a.p, b.as<float>(), W, H, tp, mmp));
+        if (used == BLUR_NONE) return fail(SIFTMI_EINVAL, "no fused blur for input format %d", in_dtype);
     } else {
-        const int r = norm ? launch_blur_tiled<true>(opt, 0, a.as<float>(), b.as<float>(), W, H, tp, mmp)
-                           : launch_blur_tiled<false>(opt, 0, a.as<float>(), b.as<float>(), W, H, tp, mmp);
-        if (!r) launch_blur_generic(0, a.as<float>(), b.as<float>(), t.as<float>(), W, H, tp, mmp, norm != 0);
-        else {
-            bool marchable = false;
-            for (int n : {11, 15, 17, 21, 27}) marchable = marchable || n == ntaps;
-            used = (march_plane(W, H) && taps_symmetric(tp) && opt.march && marchable) ? 2 : 1;
-        }
+        used = norm ? launch_blur_tiled<true>(opt, 0, a.as<float>(), b.as<float>(), W, H, tp, mmp)
+                    : launch_blur_tiled<false>(opt, 0, a.as<float>(), b.as<float>(), W, H, tp, mmp);
+        if (used == BLUR_NONE) launch_blur_generic(0, a.as<float>(), b.as<float>(), t.as<float>(), W, H, tp, mmp, norm != 0);
     }
     if ((rc = stage_end())) return rc;
     if (kernel_used) *kernel_used = used;
