@@ -277,6 +277,33 @@ int siftmi_stage_orientation(int32_t device_id, const float *blurs, int32_t W, i
                              float *out, int32_t *out_scale, int64_t capacity, int64_t *n_out);
 int siftmi_stage_descriptor(int32_t device_id, const float *blurs, int32_t W, int32_t H, int32_t octsize,
                             const float *kps, const int32_t *kp_scale, int64_t n, uint8_t *desc);
+/* The two stages above with a plan's launch choices exposed (test hooks: every form of the per-keypoint kernels).  The
+ * entry points above are these with form = 0, blocks = 0.  Extra arguments:
+ *   form        orientation: 0 the stage's form (a wave per keypoint), 1 a wave per keypoint, 2 a workgroup per keypoint;
+ *               descriptor: 0 the stage's rule (row-interval wave form, the streaming form where a window has R > 127),
+ *               1 row-interval, a wave per keypoint, 2 row-interval, a workgroup per keypoint, 3 streaming.
+ *               + 4: the MAPS instance (orientation: any form; descriptor: forms 1 and 2 only): the stage first builds the
+ *               gradient maps of planes 1..3 with the plan's map kernel, in the plan's layout, and the kernel reads them.
+ *   blocks      workgroups of the launch (0: the stage's grid); also passed as the kernel's count-based cuts, so it holds.
+ *   *form_used  (may be null) the form the launch selects, + 4 for MAPS (descriptor with n == 0: nothing launched, 0): the
+ *               kernel launched, and for the two row forms the kernel's own count rule applied to the arguments it was given
+ *               (the kernel does not report the form back).
+ * SIFTMI_EINVAL, nothing launched and nothing written, for an unknown form, blocks < 0, MAPS with a detection scale outside
+ * 1..3, MAPS with the streaming form, or a row-interval form for a list that holds a window of R > 127. */
+int siftmi_stage_orientation_ex(int32_t device_id, const float *blurs, int32_t W, int32_t H, int32_t octsize,
+                                const float *kps, const int32_t *kp_scale, int64_t n, const siftmi_params *params,
+                                float *out, int32_t *out_scale, int64_t capacity, int64_t *n_out,
+                                int32_t form, int32_t blocks, int32_t *form_used);
+int siftmi_stage_descriptor_ex(int32_t device_id, const float *blurs, int32_t W, int32_t H, int32_t octsize,
+                               const float *kps, const int32_t *kp_scale, int64_t n, uint8_t *desc,
+                               int32_t form, int32_t blocks, int32_t *form_used);
+/* The gradient-map kernel of the MAPS forms (image.cl:47-80 on planes 1..3 of every octave) over a pyramid of n_oct
+ * octaves, octave o of W[o] x H[o] pixels.  planes: six planes per octave, back to back (a plan's plane buffer);
+ * gmap / omap: three planes per octave, octave o from float 3 * sum_{p < o} W[p] H[p] (half of its plane offset).
+ * Only the octaves [oct_lo, oct_hi) are computed; both maps are uploaded first and read back whole, so the others keep
+ * what the caller put there.  blocks: workgroups of the grid stride (0: the plan's default). */
+int siftmi_stage_gradient_maps(int32_t device_id, const float *planes, int32_t n_oct, const int32_t *W, const int32_t *H,
+                               int32_t oct_lo, int32_t oct_hi, int32_t blocks, float *gmap, float *omap);
 int siftmi_stage_shrink(int32_t device_id, const float *in, float *out, int32_t W, int32_t H);
 int siftmi_stage_convert(int32_t device_id, const void *in, int32_t in_dtype, float *out, int32_t W, int32_t H);
 /* device versions of the "siftmath v1" functions, elementwise over n floats (test hook) */

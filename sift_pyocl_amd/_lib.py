@@ -103,6 +103,13 @@ _SIGNATURES = {
                                            C.c_int64, C.POINTER(C.c_int64)]),
     "siftmi_stage_descriptor": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p]),
+    "siftmi_stage_orientation_ex": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                              C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "siftmi_stage_descriptor_ex": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "siftmi_stage_gradient_maps": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "siftmi_plan_records_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "siftmi_plan_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.POINTER(C.c_double)]),

@@ -806,17 +806,23 @@ void launch_descriptor_group(siftmi_plan *p, int group, hipStream_t st) {
                            (const float4 *)G.okp, (const int *)G.oaux, p->cnt, group, 0, 0, ocap, p->records, rcap, p->host_out, p->host_cap);
 }
 
+// gradient_maps_kernel over the octaves [oct_lo, oct_hi) of `tab` into tab.gmap / tab.omap, at most `blocks` workgroups
+// walking the items with a grid stride (the plan's launch below and the stage hook siftmi_stage_gradient_maps)
+void launch_maps_kernel(const OctaveTable &tab, int oct_lo, int oct_hi, int blocks, hipStream_t st) {
+    long long total = 0;
+    for (int o = oct_lo; o < oct_hi; o++) total += gradient_map_items_of(tab.W[o], tab.H[o]);
+    if (total <= 0) return;
+    const unsigned g = (unsigned)std::min<long long>(total, blocks);
+    hipLaunchKernelGGL(gradient_maps_kernel, dim3(g), dim3(256), 0, st, tab, oct_lo, oct_hi, total, (float *)tab.gmap, (float *)tab.omap);
+}
+
 // gradient maps of the octaves [oct_lo, oct_hi) (their pyramids exist on `st`)
 void launch_gradient_maps(siftmi_plan *p, int oct_lo, int oct_hi, hipStream_t st) {
     if (oct_lo >= oct_hi) return;
-    const OctaveTable tab = octave_table(p);
-    long long total = 0;
-    for (int o = oct_lo; o < oct_hi; o++) total += gradient_map_items_of(p->ow[(size_t)o], p->oh[(size_t)o]);
     char lab[96];
     snprintf(lab, sizeof lab, "gradient maps octaves %d-%d", oct_lo, oct_hi - 1);
     Scope sc(p, lab, false, 0, st);
-    const unsigned blocks = (unsigned)std::min<long long>(total, p->opt.maps_blocks);
-    hipLaunchKernelGGL(gradient_maps_kernel, dim3(blocks), dim3(256), 0, st, tab, oct_lo, oct_hi, total, p->gmap, p->omap);
+    launch_maps_kernel(octave_table(p), oct_lo, oct_hi, p->opt.maps_blocks, st);
 }
 
 // orientation + descriptors of one group, on one stream, ending with the read-back of the counters into pinned block `slot`
@@ -2412,6 +2418,34 @@ int stage_end() {
     return SIFTMI_OK;
 }
 
+// the plan's map launch on the null stream; blocks: width of the grid stride (0: the plan's default)
+void stage_maps_launch(const OctaveTable &tab, int oct_lo, int oct_hi, int blocks) {
+    launch_maps_kernel(tab, oct_lo, oct_hi, blocks > 0 ? blocks : g_default_options.maps_blocks, 0);
+}
+
+// octave of a power-of-two octsize
+int stage_octave(int32_t octsize, int &oct) {
+    oct = 0;
+    while ((1 << oct) < octsize && oct < SIFT_MAX_OCTAVES - 1) oct++;
+    return (1 << oct) == octsize ? SIFTMI_OK : fail(SIFTMI_EINVAL, "octsize must be a power of two");
+}
+
+// the MAPS forms read the maps of detection scales 1..3 only
+int stage_maps_scales(const int32_t *kp_scale, int64_t n) {
+    for (int64_t i = 0; i < n; i++)
+        if (kp_scale[i] < 1 || kp_scale[i] > 3)
+            return fail(SIFTMI_EINVAL, "gradient maps hold detection scales 1..3 only (keypoint %lld: %d)", (long long)i, kp_scale[i]);
+    return SIFTMI_OK;
+}
+
+// Does the window of an oriented keypoint fit the row tables of the row-interval forms (R <= SIFT_DESC_MAXRAD)?  The
+// kernels' expressions (desc_window, keypoints_cpu.cl:57-62); the float is compared instead of its (int) conversion, which
+// is undefined on the host beyond the int range (an infinite spacing would pass as INT_MIN and reach the kernel's trap).
+bool desc_rows_fit(float sigma_oct, int32_t octsize) {
+    const float spacing = sigma_oct / (float)octsize * 3.0f;
+    return !((1.414f * spacing * 2.5f) + 0.5f >= (float)(SIFT_DESC_MAXRAD + 1));
+}
+
 }  // namespace
 
 extern "C" {
@@ -2607,28 +2641,52 @@ int siftmi_stage_gradient(int32_t dev, const float *img, float *grad, float *ori
 int siftmi_stage_orientation(int32_t dev, const float *blurs, int32_t W, int32_t H, int32_t octsize, const float *kps,
                              const int32_t *kp_scale, int64_t n, const siftmi_params *par, float *out,
                              int32_t *out_scale, int64_t capacity, int64_t *n_out) {
+    return siftmi_stage_orientation_ex(dev, blurs, W, H, octsize, kps, kp_scale, n, par, out, out_scale, capacity, n_out, 0, 0, nullptr);
+}
+
+int siftmi_stage_orientation_ex(int32_t dev, const float *blurs, int32_t W, int32_t H, int32_t octsize, const float *kps,
+                                const int32_t *kp_scale, int64_t n, const siftmi_params *par, float *out,
+                                int32_t *out_scale, int64_t capacity, int64_t *n_out, int32_t form, int32_t blocks, int32_t *form_used) {
     int rc = stage_begin(dev); if (rc) return rc;
     if (!par || !n_out) return fail(SIFTMI_EINVAL, "null argument");
+    if (form < 0 || form > 7 || (form & 3) == 3) return fail(SIFTMI_EINVAL, "orientation form %d: 0 / 1 wave, 2 workgroup per keypoint, + 4 maps", form);
+    if (blocks < 0) return fail(SIFTMI_EINVAL, "blocks must not be negative");
+    const bool maps = (form & 4) != 0;
+    if (maps && (rc = stage_maps_scales(kp_scale, n))) return rc;
+    int oct;
+    if ((rc = stage_octave(octsize, oct))) return rc;
     const size_t N = (size_t)W * H;
-    DevBuf b, k, ks, o, oa, cnt;
+    DevBuf b, k, ks, o, oa, cnt, gm, om;
     if ((rc = b.upload(blurs, 6 * N * 4)) || (rc = k.upload(kps, (size_t)n * 16)) || (rc = ks.upload(kp_scale, (size_t)n * 4)) ||
         (rc = o.alloc((size_t)capacity * 16)) || (rc = oa.alloc((size_t)capacity * 4)) || (rc = cnt.alloc(sizeof(Counters)))) return rc;
+    if (maps && ((rc = gm.alloc(3 * N * 4)) || (rc = om.alloc(3 * N * 4)))) return rc;
     Counters hc{};
     hc.g_kp[0] = (int)n;
     HIPCHK(hipMemcpy(cnt.p, &hc, sizeof hc, hipMemcpyHostToDevice));
-    int oct = 0;
-    while ((1 << oct) < octsize && oct < SIFT_MAX_OCTAVES - 1) oct++;
-    if ((1 << oct) != octsize) return fail(SIFTMI_EINVAL, "octsize must be a power of two");
     OctaveTable tab;
     memset(&tab, 0, sizeof tab);
     tab.base = b.as<float>(); tab.off[oct] = 0; tab.W[oct] = W; tab.H[oct] = H;
+    tab.gmap = gm.as<float>(); tab.omap = om.as<float>();
     std::vector<int32_t> aux((size_t)n);
     for (int64_t i = 0; i < n; i++) aux[(size_t)i] = kp_scale[i] | (oct << 8);
     HIPCHK(hipMemcpy(ks.p, aux.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(orientation_kernel<false>, dim3(grid_for(n * 64, 256, 1024)), dim3(256), 0, 0, tab,
-                       par->ori_sigma, (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), cnt.as<Counters>(), 0, (int)n,
-                       o.as<float4>(), oa.as<int>(), (int)capacity, 0, 512);
+    if (maps) stage_maps_launch(tab, oct, oct + 1, 0);
+    // a workgroup per keypoint below `team_below` keypoints; `blocks` is also the small-group cut, which would override the grid
+    const int team_below = (form & 3) == 2 ? (1 << 30) : 0;
+    const int grid = blocks > 0 ? blocks : grid_for(n * 64, 256, 1024), small_blocks = blocks > 0 ? blocks : 512;
+    if (maps)
+        hipLaunchKernelGGL(orientation_kernel<true>, dim3(grid), dim3(256), 0, 0, tab,
+                           par->ori_sigma, (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), cnt.as<Counters>(), 0, (int)n,
+                           o.as<float4>(), oa.as<int>(), (int)capacity, team_below, small_blocks);
+    else
+        hipLaunchKernelGGL(orientation_kernel<false>, dim3(grid), dim3(256), 0, 0, tab,
+                           par->ori_sigma, (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), cnt.as<Counters>(), 0, (int)n,
+                           o.as<float4>(), oa.as<int>(), (int)capacity, team_below, small_blocks);
+    // What the launch arguments select: the kernel takes the workgroup form when its count (here n) is below team_below.
+    // The kernel reports nothing back, so this is the kernel's rule applied on the host, not an observation of the launch.
+    const int used = ((int)n < team_below ? 2 : 1) | (maps ? 4 : 0);
     if ((rc = stage_end())) return rc;
+    if (form_used) *form_used = used;
     HIPCHK(hipMemcpy(&hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost));
     int64_t m = hc.g_out[0] < capacity ? hc.g_out[0] : capacity;
     if (m > 0) {
@@ -2642,40 +2700,89 @@ int siftmi_stage_orientation(int32_t dev, const float *blurs, int32_t W, int32_t
 
 int siftmi_stage_descriptor(int32_t dev, const float *blurs, int32_t W, int32_t H, int32_t octsize, const float *kps,
                             const int32_t *kp_scale, int64_t n, uint8_t *desc) {
+    return siftmi_stage_descriptor_ex(dev, blurs, W, H, octsize, kps, kp_scale, n, desc, 0, 0, nullptr);
+}
+
+int siftmi_stage_descriptor_ex(int32_t dev, const float *blurs, int32_t W, int32_t H, int32_t octsize, const float *kps,
+                               const int32_t *kp_scale, int64_t n, uint8_t *desc, int32_t form, int32_t blocks, int32_t *form_used) {
     int rc = stage_begin(dev); if (rc) return rc;
+    const int kind = form & 3;
+    const bool maps = (form & 4) != 0;
+    if (form < 0 || form > 7 || (maps && (kind == 0 || kind == 3)))
+        return fail(SIFTMI_EINVAL, "descriptor form %d: 0 by window size, 1 wave, 2 workgroup per keypoint, 3 streaming, + 4 maps (1, 2)", form);
+    if (blocks < 0) return fail(SIFTMI_EINVAL, "blocks must not be negative");
+    if (maps && (rc = stage_maps_scales(kp_scale, n))) return rc;
+    int oct;
+    if ((rc = stage_octave(octsize, oct))) return rc;
+    bool rows_fit = true;
+    for (int64_t i = 0; i < n; i++) rows_fit = rows_fit && desc_rows_fit(kps[4 * i + 2], octsize);
+    if ((kind == 1 || kind == 2) && !rows_fit) return fail(SIFTMI_EINVAL, "a window of the list has R > %d: streaming form only", SIFT_DESC_MAXRAD);
+    const int use = kind ? kind : (rows_fit ? 1 : 3);
     const size_t N = (size_t)W * H;
-    DevBuf b, k, ks, r;
+    DevBuf b, k, ks, r, gm, om;
     if ((rc = b.upload(blurs, 6 * N * 4)) || (rc = k.upload(kps, (size_t)n * 16)) || (rc = ks.upload(kp_scale, (size_t)n * 4)) ||
         (rc = r.alloc((size_t)n * sizeof(KpRecord)))) return rc;
-    int oct = 0;
-    while ((1 << oct) < octsize && oct < SIFT_MAX_OCTAVES - 1) oct++;
-    if ((1 << oct) != octsize) return fail(SIFTMI_EINVAL, "octsize must be a power of two");
+    if (maps && ((rc = gm.alloc(3 * N * 4)) || (rc = om.alloc(3 * N * 4)))) return rc;
+    // every form writes every record, that of a hole or of a window without samples included: a record it drops shows as 0xa5 bytes
+    if (n > 0) HIPCHK(hipMemset(r.p, 0xa5, (size_t)n * sizeof(KpRecord)));
     OctaveTable tab;
     memset(&tab, 0, sizeof tab);
     tab.base = b.as<float>(); tab.off[oct] = 0; tab.W[oct] = W; tab.H[oct] = H;
+    tab.gmap = gm.as<float>(); tab.omap = om.as<float>();
     std::vector<int32_t> aux((size_t)n);
     for (int64_t i = 0; i < n; i++) aux[(size_t)i] = kp_scale[i] | (oct << 8);
+    int used = 0;
     if (n > 0) {
         HIPCHK(hipMemcpy(ks.p, aux.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        // row-interval form unless a window is too large for its row tables (same expressions as the kernel: keypoints_cpu.cl:57-62)
-        bool block_ok = true;
-        for (int64_t i = 0; i < n; i++) {
-            const float spacing = kps[4 * i + 2] / (float)octsize * 3.0f;
-            if (!((int)((1.414f * spacing * 2.5f) + 0.5f) <= SIFT_DESC_MAXRAD)) block_ok = false;
-        }
-        if (block_ok)
-            hipLaunchKernelGGL(descriptor_kernel<false>, dim3(grid_for(n, 4, 2048)), dim3(256), 0, 0, tab,
-                               (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), (Counters *)nullptr, 0, 0, (int)n,
-                               (int)n, r.as<KpRecord>(), (int)n, (KpRecord *)nullptr, 0, 0, 0, 1 << 30, 1 << 30);
-        else
-            hipLaunchKernelGGL(descriptor_stream_kernel, dim3(grid_for(n, 4, 2048)), dim3(256), 0, 0, tab,
+        if (maps) stage_maps_launch(tab, oct, oct + 1, 0);
+        // `blocks` is the grid and both of the kernel's count-based cuts; a workgroup per keypoint below `team_below` keypoints
+        const int grid = blocks > 0 ? blocks : grid_for(n, 4, 2048), cut = blocks > 0 ? blocks : (1 << 30);
+        const int team_below = use == 2 ? (1 << 30) : 0;
+        if (use == 3)
+            hipLaunchKernelGGL(descriptor_stream_kernel, dim3(grid), dim3(256), 0, 0, tab,
                                (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), (Counters *)nullptr, 0, 0, (int)n,
                                (int)n, r.as<KpRecord>(), (int)n, (KpRecord *)nullptr, 0);
+        else if (maps)
+            hipLaunchKernelGGL(descriptor_kernel<true>, dim3(grid), dim3(256), 0, 0, tab,
+                               (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), (Counters *)nullptr, 0, 0, (int)n,
+                               (int)n, r.as<KpRecord>(), (int)n, (KpRecord *)nullptr, 0, team_below, 0, cut, cut);
+        else
+            hipLaunchKernelGGL(descriptor_kernel<false>, dim3(grid), dim3(256), 0, 0, tab,
+                               (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), (Counters *)nullptr, 0, 0, (int)n,
+                               (int)n, r.as<KpRecord>(), (int)n, (KpRecord *)nullptr, 0, team_below, 0, cut, cut);
+        // what the launch selects (the kernel's own rule, count < team_below, applied here: the kernel reports nothing back)
+        used = (use == 3 ? 3 : ((int)n < team_below ? 2 : 1)) | (maps ? 4 : 0);
     }
     if ((rc = stage_end())) return rc;
+    if (form_used) *form_used = used;
     std::vector<KpRecord> h((size_t)n);
     if (n > 0) HIPCHK(hipMemcpy(h.data(), r.p, (size_t)n * sizeof(KpRecord), hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < n; i++) memcpy(desc + (size_t)i * 128, h[(size_t)i].desc, 128);
+    return SIFTMI_OK;
+}
+
+int siftmi_stage_gradient_maps(int32_t dev, const float *planes, int32_t n_oct, const int32_t *W, const int32_t *H,
+                               int32_t oct_lo, int32_t oct_hi, int32_t blocks, float *gmap, float *omap) {
+    int rc = stage_begin(dev); if (rc) return rc;
+    if (!planes || !W || !H || !gmap || !omap) return fail(SIFTMI_EINVAL, "null argument");
+    if (n_oct < 1 || n_oct > SIFT_MAX_OCTAVES) return fail(SIFTMI_EINVAL, "n_oct must be in 1..%d", SIFT_MAX_OCTAVES);
+    if (oct_lo < 0 || oct_hi < oct_lo || oct_hi > n_oct) return fail(SIFTMI_EINVAL, "octave range [%d, %d) outside [0, %d)", oct_lo, oct_hi, n_oct);
+    if (blocks < 0) return fail(SIFTMI_EINVAL, "blocks must not be negative");
+    OctaveTable tab;
+    memset(&tab, 0, sizeof tab);
+    size_t total = 0;                    // floats of the plane buffer (the maps: half of it)
+    for (int o = 0; o < n_oct; o++) {
+        if (W[o] < 1 || H[o] < 1 || (int64_t)W[o] * H[o] > (1 << 30)) return fail(SIFTMI_EINVAL, "octave %d: bad size %d x %d", o, W[o], H[o]);
+        tab.off[o] = (long long)total; tab.W[o] = W[o]; tab.H[o] = H[o];
+        total += 6 * (size_t)W[o] * H[o];
+    }
+    DevBuf b, gm, om;
+    if ((rc = b.upload(planes, total * 4)) || (rc = gm.upload(gmap, total / 2 * 4)) || (rc = om.upload(omap, total / 2 * 4))) return rc;
+    tab.base = b.as<float>(); tab.gmap = gm.as<float>(); tab.omap = om.as<float>();
+    stage_maps_launch(tab, oct_lo, oct_hi, blocks);
+    if ((rc = stage_end())) return rc;
+    HIPCHK(hipMemcpy(gmap, gm.p, total / 2 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(omap, om.p, total / 2 * 4, hipMemcpyDeviceToHost));
     return SIFTMI_OK;
 }
 

@@ -10,7 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from util import (assert_same_keypoints, multiscale_noise, rectangles, smooth_noise, sort_rows, white_noise)
+from util import (assert_same_keypoints, descriptor_edge_rows, descriptor_random_rows, multiscale_noise, orientation_border_rows,
+                  rectangles, smooth_noise, sort_rows, white_noise)
 
 pytestmark = pytest.mark.gpu
 
@@ -322,25 +323,7 @@ def test_descriptor_windows_at_their_edges(siftlib, oracle, octsize):
     blurs = _octave_blurs(oracle, img)
     s = 2
     eg, eo = oracle.gradient(blurs[s])
-    pi = float(np.float32(np.pi))
-    angles = []
-    for a in (0.0, pi / 4, pi / 2, 3 * pi / 4, pi, -pi / 4, -pi / 2, -3 * pi / 4, -pi):
-        for eps in (0.0, 1e-6, -1e-6, 1e-3):
-            angles.append(np.float32(a + eps))
-    angles += [np.float32(0.3), np.float32(-2.9), np.float32(1.1), np.float32(2.5)]
-    sigmas = [0.8, 1.6, 2.2, 3.17, 4.5, 7.0, 11.9]          # window radius 4 ... 126 pixels of the octave
-    centres = [(210.0, 150.0), (210.5, 150.5), (3.0, 4.0), (0.0, 0.0), (W - 1.0, H - 1.0), (W - 2.5, 40.25), (60.75, H - 1.5),
-               (-6.0, 100.0), (W + 9.0, H + 9.0), (200.0, -3.0)]
-    rows = []
-    k = 0
-    for sg in sigmas:
-        for (cx, cy) in centres:
-            for j in range(4):
-                ang = angles[k % len(angles)]; k += 1
-                rows.append((cx * octsize, cy * octsize, sg * octsize, ang))
-    for ang in angles:                                      # every angle once on the mid-size window in the middle of the plane
-        rows.append((123.25 * octsize, 77.75 * octsize, 2.9 * octsize, ang))
-    kk = np.ascontiguousarray(np.array(rows, np.float32))
+    kk = descriptor_edge_rows(W, H, octsize)
     want = oracle.descriptor(kk, eg, eo, octsize, 0, len(kk))
     ss = np.full(len(kk), s, np.int32)
     got = np.zeros((len(kk), 128), np.uint8)
@@ -355,18 +338,12 @@ def test_descriptor_random_keypoints(siftlib, oracle, seed, octsize, shape):
     """3000 random oriented keypoints per case (uniform centres up to 8 pixels beyond the plane, log-uniform sigma from the
     smallest window to R = 126, uniform angle in [-pi, pi]): the descriptor stage against the oracle, every bin."""
     H, W = shape
-    rng = np.random.default_rng(seed)
     img = multiscale_noise((H, W)) if seed != 2 else white_noise((H, W))
     blurs = _octave_blurs(oracle, img)
     s = 1 + seed % 3
     eg, eo = oracle.gradient(blurs[s])
     n = 3000
-    kk = np.empty((n, 4), np.float32)
-    kk[:, 0] = rng.uniform(-8, W + 8, n) * octsize
-    kk[:, 1] = rng.uniform(-8, H + 8, n) * octsize
-    kk[:, 2] = np.exp(rng.uniform(np.log(0.4), np.log(11.9), n)) * octsize
-    kk[:, 3] = rng.uniform(-np.pi, np.pi, n)
-    kk[::97, 3] = np.float32(np.pi); kk[1::97, 3] = -np.float32(np.pi); kk[2::97, 3] = 0.0
+    kk = descriptor_random_rows(seed, W, H, octsize, n)
     want = oracle.descriptor(kk, eg, eo, octsize, 0, n)
     ss = np.full(n, s, np.int32)
     got = np.zeros((n, 128), np.uint8)
@@ -386,12 +363,7 @@ def test_orientation_windows_at_the_borders(siftlib, oracle):
     opar = oracle.default_params()
     s = 1
     eg, eo = oracle.gradient(blurs[s])
-    rows = []
-    for sg in (0.5, 1.0, 1.6, 2.5, 4.5, 8.0):
-        for (r, c) in [(150.0, 210.0), (150.5, 210.5), (0.0, 0.0), (1.0, 2.0), (H - 1.0, W - 1.0), (H - 2.0, 3.0), (5.25, W - 1.75),
-                       (H / 2.0, 0.0), (0.0, W / 2.0), (H - 1.0, W / 2.0), (77.75, 123.25)]:
-            rows.append((12.0, r, c, sg))
-    sel = np.ascontiguousarray(np.array(rows, np.float32))
+    sel = orientation_border_rows(W, H)
     buf = np.full((len(sel) * 8 + 8, 4), -1, np.float32); buf[:len(sel)] = sel
     okp, cnt = oracle.orientation(buf, eg, eo, 1, 0, len(sel), capacity=len(buf), par=opar)
     okp = okp[:cnt]

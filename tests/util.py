@@ -32,6 +32,57 @@ def rectangles(shape, seed=7, n=60):
     return img
 
 
+# ---- synthetic keypoint lists of the per-keypoint stages (tests/test_gpu_parity.py, tests/test_gpu_keypoint_forms.py)
+def descriptor_edge_rows(W, H, octsize):
+    """Oriented keypoints (x, y, sigma, angle) of an octave of size `octsize` chosen to stress the row-interval descriptor
+    form (k_descriptor.hpp): window axes on and a hair off the pixel axes and diagonals (rows that start / end exactly on a
+    cell boundary, the short rows at the corners of a 45-degree window), window radius 4 ... 126, centres on, next to and
+    beyond the borders of a W x H plane (clipped rows, empty rows, empty windows), sub-pixel offsets of exactly one half."""
+    pi = float(np.float32(np.pi))
+    angles = []
+    for a in (0.0, pi / 4, pi / 2, 3 * pi / 4, pi, -pi / 4, -pi / 2, -3 * pi / 4, -pi):
+        for eps in (0.0, 1e-6, -1e-6, 1e-3):
+            angles.append(np.float32(a + eps))
+    angles += [np.float32(0.3), np.float32(-2.9), np.float32(1.1), np.float32(2.5)]
+    sigmas = [0.8, 1.6, 2.2, 3.17, 4.5, 7.0, 11.9]          # window radius 4 ... 126 pixels of the octave
+    centres = [(210.0, 150.0), (210.5, 150.5), (3.0, 4.0), (0.0, 0.0), (W - 1.0, H - 1.0), (W - 2.5, 40.25), (60.75, H - 1.5),
+               (-6.0, 100.0), (W + 9.0, H + 9.0), (200.0, -3.0)]
+    rows = []
+    k = 0
+    for sg in sigmas:
+        for (cx, cy) in centres:
+            for j in range(4):
+                ang = angles[k % len(angles)]; k += 1
+                rows.append((cx * octsize, cy * octsize, sg * octsize, ang))
+    for ang in angles:                                      # every angle once on the mid-size window in the middle of the plane
+        rows.append((123.25 * octsize, 77.75 * octsize, 2.9 * octsize, ang))
+    return np.ascontiguousarray(np.array(rows, np.float32))
+
+
+def descriptor_random_rows(seed, W, H, octsize, n=3000):
+    """n random oriented keypoints of an octave of size `octsize`: uniform centres up to 8 pixels beyond a W x H plane,
+    log-uniform sigma from the smallest window to R = 126, uniform angle in [-pi, pi] (and exactly pi, -pi, 0 every 97th)."""
+    rng = np.random.default_rng(seed)
+    kk = np.empty((n, 4), np.float32)
+    kk[:, 0] = rng.uniform(-8, W + 8, n) * octsize
+    kk[:, 1] = rng.uniform(-8, H + 8, n) * octsize
+    kk[:, 2] = np.exp(rng.uniform(np.log(0.4), np.log(11.9), n)) * octsize
+    kk[:, 3] = rng.uniform(-np.pi, np.pi, n)
+    kk[::97, 3] = np.float32(np.pi); kk[1::97, 3] = -np.float32(np.pi); kk[2::97, 3] = 0.0
+    return kk
+
+
+def orientation_border_rows(W, H):
+    """Refined keypoints (peak, row, col, sigma) whose orientation windows are clipped by every border and corner of a
+    W x H plane: sigma 0.5 ... 8 (radius 2 ... 36), centres on half-pixel positions."""
+    rows = []
+    for sg in (0.5, 1.0, 1.6, 2.5, 4.5, 8.0):
+        for (r, c) in [(150.0, 210.0), (150.5, 210.5), (0.0, 0.0), (1.0, 2.0), (H - 1.0, W - 1.0), (H - 2.0, 3.0), (5.25, W - 1.75),
+                       (H / 2.0, 0.0), (0.0, W / 2.0), (H - 1.0, W / 2.0), (77.75, 123.25)]:
+            rows.append((12.0, r, c, sg))
+    return np.ascontiguousarray(np.array(rows, np.float32))
+
+
 def sort_kp(k):
     """Keypoint order is unspecified (atomic append in the reference, plan.py:3.2): compare sorted."""
     k = np.asarray(k)
