@@ -237,7 +237,8 @@ int siftmi_match_last_kernel_ms(const siftmi_matcher *plan, float *ms);
 int siftmi_match_last_stage_ms(const siftmi_matcher *plan, float *ms4);
 int siftmi_match_destroy(siftmi_matcher *plan);
 
-/* ---- per-stage entry points (host pointers in/out; golden-vector replay, one reference kernel each)
+/* ---- per-stage entry points (host pointers in/out; golden-vector replay, one reference kernel each; the *_ex ones
+ * launch a plan's own forms of a stage with its launch choices exposed: blur_ex, detect_ex, orientation_ex, descriptor_ex)
  * gaussian.cl:56 | reductions.cl:62-241 + preprocess.cl:239 | convolution.cl:16,62 | algebra.cl:18 |
  * image.cl:119 | image.cl:235 + algebra.cl:57 | image.cl:47 | orientation_cpu.cl:41 |
  * keypoints_cpu.cl:36 | preprocess.cl:267 | preprocess.cl:53-223 */
@@ -267,6 +268,29 @@ int siftmi_stage_local_maxmin(int32_t device_id, const float *blurs, int32_t W, 
 /* candidates (n,4) -> refined (peak,row,col,sigma) + detection scale, holes removed */
 int siftmi_stage_interp(int32_t device_id, const float *blurs, int32_t W, int32_t H, const float *cand, int64_t n,
                         const siftmi_params *params, float *out, int32_t *out_scale, int64_t *n_out);
+/* The two stages above with a plan's launch choices exposed (test hook: both forms of the extrema kernel, its strip
+ * geometry, the band arguments, lists cut at their capacity).  Extra arguments:
+ *   form           0: extrema_kernel<false> fills the candidate list, then refine_kernel runs on the device-side list, as a
+ *                  plan chains them; 1: extrema_kernel<true>, the fused form (no candidate list: `cand` keeps its fill).
+ *   rows           rows of a strip (0: by the plan's size rule); xcd_map: workgroup order (option "xcd_map")
+ *   y_lo, y_hi     rows [y_lo, y_hi) of the detection area [border_dist, H - border_dist) only; y_lo = -1: all of it
+ *   cand_capacity  slots of the candidate list the kernels are told of; kp_capacity: those of the refined list.  Each list
+ *                  is followed by SIFTMI_STAGE_GUARD more slots the kernels are not told of, returned with it.
+ *   cand           (cand_capacity + guard, 4) candidates (value, row, col, scale), form 0
+ *   kp, kp_aux     (kp_capacity + guard, 4) refined (peak, row, col, sigma) and as many words: detection scale | octave << 8
+ *   counters       5 raw device counters, not cut at a capacity: candidates appended (form 0; 0 in form 1), refined keypoints
+ *                  appended, candidates read by the refinement per detection scale 1, 2, 3 (what the capacity rule is
+ *                  evaluated from; in form 0 those of the candidates that were stored).
+ * The lists are filled before the launch and returned whole -- the candidates with -1.0f (holes, the reference's fill: the
+ * refinement skips them), the refined lists with 0xa5 bytes: a slot beyond a counter, beyond what a cut list holds, or one a
+ * kernel reserved and did not write, comes back as the fill.  A plane with W or H <= 2 * border_dist launches nothing.
+ * SIFTMI_EINVAL, nothing launched, for an unknown form, rows outside 0..4096, an octsize that is no power of two,
+ * border_dist < 1 or a band that is empty or not inside the detection area. */
+#define SIFTMI_STAGE_GUARD 64
+int siftmi_stage_detect_ex(int32_t device_id, const float *blurs, int32_t W, int32_t H, int32_t octsize,
+                           const siftmi_params *params, int32_t form, int32_t rows, int32_t xcd_map, int32_t y_lo, int32_t y_hi,
+                           int64_t cand_capacity, int64_t kp_capacity, float *cand, float *kp, int32_t *kp_aux,
+                           int32_t *counters);
 /* `compact` (openCL/algebra.cl:57-84, host side plan.py:758-795): rows [start, end) of kps (n,4) whose row field is not
  * -1 are moved up to follow the first `start` rows; out receives *n_out rows (start + survivors), survivors unordered */
 int siftmi_stage_compact(int32_t device_id, const float *kps, int64_t n, int64_t start, int64_t end, float *out, int64_t *n_out);

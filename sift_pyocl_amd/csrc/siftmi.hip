@@ -2605,6 +2605,75 @@ int siftmi_stage_interp(int32_t dev, const float *blurs, int32_t W, int32_t H, c
     return SIFTMI_OK;
 }
 
+// The detection stage with a plan's launch choices exposed (launch_detect_octave), so that a stage test reaches both forms
+// of the extrema kernel at every strip height, both workgroup orders, the band arguments and lists cut at their capacity.
+// Counters come back raw (what the kernels counted, not what fits); the output lists are filled before the launch (the
+// candidates with -1.0f, the refined lists with 0xa5 bytes) and copied back whole, guard slots included, so a slot no
+// kernel wrote shows.
+int siftmi_stage_detect_ex(int32_t dev, const float *blurs, int32_t W, int32_t H, int32_t octsize, const siftmi_params *par,
+                           int32_t form, int32_t rows, int32_t xcd_map, int32_t y_lo, int32_t y_hi,
+                           int64_t cand_capacity, int64_t kp_capacity, float *cand, float *kp, int32_t *kp_aux, int32_t *counters) {
+    int rc = stage_begin(dev); if (rc) return rc;
+    if (!blurs || !par || !counters || !cand || !kp || !kp_aux) return fail(SIFTMI_EINVAL, "null argument");
+    if (W < 1 || H < 1) return fail(SIFTMI_EINVAL, "empty plane");
+    if (form != 0 && form != 1) return fail(SIFTMI_EINVAL, "detection form %d: 0 extrema then refinement launch, 1 fused refinement", form);
+    if (rows < 0 || rows > 4096) return fail(SIFTMI_EINVAL, "strip rows must be in 0..4096 (0: by the size rule)");
+    if (cand_capacity < 0 || kp_capacity < 0 || cand_capacity > (1 << 30) || kp_capacity > (1 << 30)) return fail(SIFTMI_EINVAL, "capacity out of range");
+    const int border = par->border_dist;
+    if (border < 1) return fail(SIFTMI_EINVAL, "border_dist must be at least 1 (the 3 x 3 neighbourhood)");
+    const bool band = y_lo >= 0;
+    if (band && !(y_lo >= border && y_lo < y_hi && y_hi <= H - border))
+        return fail(SIFTMI_EINVAL, "band [%d, %d) outside the detection rows [%d, %d)", y_lo, y_hi, border, H - border);
+    int oct;
+    if ((rc = stage_octave(octsize, oct))) return rc;
+    const size_t N = (size_t)W * H;
+    // every list is followed by guard slots the kernels are not told about: a write beyond the capacity shows in them
+    const size_t cslots = (size_t)cand_capacity + SIFTMI_STAGE_GUARD, kslots = (size_t)kp_capacity + SIFTMI_STAGE_GUARD;
+    DevBuf b, c, k, ka, cnt;
+    if ((rc = b.upload(blurs, 6 * N * 4)) || (rc = c.alloc(cslots * 16)) || (rc = k.alloc(kslots * 16)) ||
+        (rc = ka.alloc(kslots * 4)) || (rc = cnt.alloc(sizeof(Counters)))) return rc;
+    HIPCHK(hipMemset(cnt.p, 0, sizeof(Counters)));
+    {   // (the candidate list is filled with holes, the reference's own fill: the refinement launch skips a slot the extrema
+        // kernel reserved and did not write, where a 0xa5 pattern would send it to row 0 of the plane and above it)
+        std::vector<float> holes(cslots * 4, -1.0f);
+        HIPCHK(hipMemcpy(c.p, holes.data(), cslots * 16, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemset(k.p, 0xa5, kslots * 16));
+    HIPCHK(hipMemset(ka.p, 0xa5, kslots * 4));
+    BlurPlanes bp;
+    for (int s = 0; s < 6; s++) bp.p[s] = b.as<float>() + (size_t)s * N;
+    Counters *dc = cnt.as<Counters>();
+    if (W > 2 * border && H > 2 * border) {
+        // launch_detect_octave's geometry; a band is marched as a detection area of its own
+        const int use_rows = rows > 0 ? rows : extrema_strip_rows(W, H, border, g_default_options.ext_strips);
+        const int area = band ? y_hi - y_lo : H - 2 * border;
+        const int nx = (W - 2 * border + 61) / 62, ny = (area + use_rows - 1) / use_rows;
+        const int blocks = std::max(1, (nx * ny + 3) / 4);
+        const float edth = (octsize <= 1) ? par->edge_thresh0 : par->edge_thresh;
+        const RefineArgs ra = {par->peak_thresh, (float)par->init_sigma, k.as<float4>(), ka.as<int>(), &dc->g_kp[0], (int)kp_capacity, oct, &dc->c_scale[0][0]};
+        const int yl = band ? y_lo : -1, yh = band ? y_hi : -1;
+        if (form == 1) {
+            hipLaunchKernelGGL(extrema_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, 0, bp, W, H, border, use_rows,
+                               contrast_threshold(*par), edth, c.as<float4>(), &dc->n_cand[0], (int)cand_capacity, ra, yl, yh, xcd_map ? 1 : 0);
+        } else {
+            hipLaunchKernelGGL(extrema_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, 0, bp, W, H, border, use_rows,
+                               contrast_threshold(*par), edth, c.as<float4>(), &dc->n_cand[0], (int)cand_capacity, ra, yl, yh, xcd_map ? 1 : 0);
+            hipLaunchKernelGGL(refine_kernel, dim3(512), dim3(256), 0, 0, bp, W, H, (const float4 *)c.as<float4>(),
+                               (const int *)&dc->n_cand[0], (int)cand_capacity, par->peak_thresh, (float)par->init_sigma, k.as<float4>(),
+                               ka.as<int>(), &dc->g_kp[0], (int)kp_capacity, oct, &dc->c_scale[0][0]);
+        }
+    }
+    if ((rc = stage_end())) return rc;
+    Counters hc;
+    HIPCHK(hipMemcpy(&hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost));
+    counters[0] = hc.n_cand[0]; counters[1] = hc.g_kp[0];
+    for (int s = 0; s < 3; s++) counters[2 + s] = hc.c_scale[0][s];
+    HIPCHK(hipMemcpy(cand, c.p, cslots * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(kp, k.p, kslots * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(kp_aux, ka.p, kslots * 4, hipMemcpyDeviceToHost));
+    return SIFTMI_OK;
+}
+
 int siftmi_stage_compact(int32_t dev, const float *kps, int64_t n, int64_t start, int64_t end, float *out, int64_t *n_out) {
     int rc = stage_begin(dev); if (rc) return rc;
     if (!n_out || start < 0 || end < start || end > n) return fail(SIFTMI_EINVAL, "bad range");

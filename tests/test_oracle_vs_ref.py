@@ -1,16 +1,17 @@
 """CPU test: the oracle against the reference's own kernels run natively, on inputs that are NOT in the golden set
 of tests/test_oracle_golden.py.  The reference's outputs are stored in tests/golden/ref_xcheck.npz / .json (generator
 tests/golden/make_ref_xcheck.py, run where the reference's kernels can be built: oracle/_ref), so the test needs
-neither the reference nor its native build."""
+neither the reference nor its native build.  One test does: test_detection_on_crafted_planes_identical calls the
+reference's detection kernels directly and runs where oracle/_ref is built."""
 import json
 import os
 
 import numpy as np
 import pytest
 
-from util import (PIPELINE_CASES, XCHECK_SIGMAS, array_digest, assert_same_keypoints, compare_keypoints_libm, converter_inputs,
-                  digest_cases, kp_digest, matching_valid_inputs, matching_valid_steps, pipeline_input, smooth_noise, sort_kp,
-                  sort_rows, transform_xcheck_cases)
+from util import (DETECT_FAMILIES, PIPELINE_CASES, XCHECK_SIGMAS, array_digest, assert_same_keypoints, compare_keypoints_libm,
+                  converter_inputs, detection_planes, digest_cases, kp_digest, matching_valid_inputs, matching_valid_steps,
+                  pipeline_input, smooth_noise, sort_kp, sort_rows, sort_rows_bits, transform_xcheck_cases)
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -105,6 +106,77 @@ def test_transform_identical(oracle, ref):
     assert len(cases) == len(digests) == 12 * 5
     for name, img, M, off, out_shape, fill, mode in cases:
         assert array_digest(oracle.transform(img, M, off, out_shape=out_shape, fill=fill, mode=mode)) == digests[name], name
+
+
+def _ref_detection_functions():
+    """(local_maxmin, interp_keypoint) over the reference's own kernels (oracle/_ref/libsiftclref_sm.so), with the
+    signatures of the oracle's stage functions."""
+    import ctypes as C
+    from oracle import pyref
+    pyref.use("siftmath")
+    try:
+        L = pyref.lib()
+    finally:
+        pyref.use("glibc")
+
+    def p(a):
+        return a.ctypes.data_as(C.c_void_p)
+
+    def local_maxmin(dogs, scale, octsize, capacity, par):
+        _, H, W = dogs.shape
+        kps = np.full((capacity, 4), -1, np.float32)
+        cnt = np.zeros(1, np.int32)
+        L.ref_local_maxmin(p(dogs), p(kps), C.c_int(par.border_dist), C.c_float(par.peak_thresh), C.c_int(octsize),
+                           C.c_float(par.edge_thresh0), C.c_float(par.edge_thresh), p(cnt), C.c_int(capacity), C.c_int(scale),
+                           C.c_int(W), C.c_int(H))
+        return kps, int(cnt[0])
+
+    def interp_keypoint(dogs, kps, start, end, par):
+        _, H, W = dogs.shape
+        kps = np.ascontiguousarray(kps, np.float32).copy()
+        L.ref_interp_keypoint(p(dogs), p(kps), C.c_int(start), C.c_int(end), C.c_float(par.peak_thresh),
+                              C.c_float(np.float32(par.init_sigma)), C.c_int(W), C.c_int(H), C.c_int(len(kps)))
+        return kps
+    return local_maxmin, interp_keypoint
+
+
+# (family, shape (H, W), octsize, border_dist): every family of util.detection_dogs at 203 x 317, the waves with both edge
+# thresholds, other borders, and the planes with a detection area of one pixel / 2 x 3 pixels
+DETECTION_XCHECK = ([(f, (203, 317), 1, 5) for f in DETECT_FAMILIES] +
+                    [("waves", (203, 317), 2, 5), ("iid", (90, 131), 2, 1), ("blocks", (90, 131), 1, 2), ("levels", (90, 131), 1, 9),
+                     ("equal+", (60, 140), 1, 5), ("equal-", (11, 11), 1, 5), ("iid", (11, 11), 1, 5), ("iid", (12, 13), 1, 5),
+                     ("equal+", (12, 13), 2, 5)])
+REF_SM = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libsiftclref_sm.so")
+
+
+@pytest.mark.skipif(not os.path.exists(REF_SM), reason="needs the native build of the reference's kernels (oracle/_ref)")
+@pytest.mark.parametrize("family,shape,octsize,border", DETECTION_XCHECK)
+def test_detection_on_crafted_planes_identical(oracle, family, shape, octsize, border):
+    """The judge of tests/test_gpu_detection_forms.py on its own inputs: so_local_maxmin / so_interp_keypoint against the
+    reference's local_maxmin / interp_keypoint kernels, bit for bit, on DoG planes full of ties, plateaus, singular
+    Hessians, samples on the contrast threshold and NaN / inf -- where the oracle could restate the reference wrongly and
+    no blurred float image would show it.  Candidates per scale (sorted: the reference appends through an atomic), the
+    counters, and every refined row, the rejected ones included."""
+    ref_lm, ref_ik = _ref_detection_functions()
+    dogs = oracle.dog(detection_planes(family, shape, seed=3))
+    H, W = shape
+    par = oracle.default_params()
+    par.border_dist = border
+    total = 0
+    for s in (1, 2, 3):
+        ko, no = oracle.local_maxmin(dogs, s, octsize, H * W, par)
+        kr, nr = ref_lm(dogs, s, octsize, H * W, par)
+        assert no == nr, "scale %d: %d vs %d candidates" % (s, no, nr)
+        co, cr = sort_rows_bits(ko[:no]), sort_rows_bits(kr[:nr])
+        assert np.array_equal(co, cr), "scale %d: candidates differ" % s
+        assert (ko[no:] == -1).all() and (kr[nr:] == -1).all()
+        cand = np.ascontiguousarray(co.view(np.float32))
+        io, ir = oracle.interp_keypoint(dogs, cand, 0, no, par), ref_ik(dogs, cand, 0, no, par)
+        assert np.array_equal(io.view(np.uint32), ir.view(np.uint32)), "scale %d: refined rows differ" % s
+        total += no
+    if family.startswith("equal"):
+        assert total == 3 * (W - 2 * border) * (H - 2 * border)        # every sample of the area, at the three scales
+    assert total > 0 or min(shape) < 20, "no candidate: the family does not stress anything"
 
 
 def test_matching_valid_identical(oracle, ref):

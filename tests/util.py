@@ -302,3 +302,99 @@ def array_digest(a):
     import hashlib
     a = np.ascontiguousarray(a)
     return hashlib.sha256(("%s %s|" % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+# ---- crafted planes of the detection stage (tests/test_gpu_detection_forms.py, tests/test_oracle_vs_ref.py)
+# Every family is a set of five DoG planes of small integers (or quarters), turned into six blur planes by
+# blur[5] = 64, blur[s] = blur[s + 1] + dog[s]: every sum and every subtraction blur[s] - blur[s + 1] is exact, so the
+# kernels see the DoG planes as generated -- with equal samples everywhere, singular Hessians and values on the contrast
+# threshold, which no blurred float image has.
+DETECT_FAMILIES = ("iid", "blocks", "repeat", "equal+", "equal-", "spikes", "levels", "waves", "nan", "+inf", "-inf", "mixed")
+DETECT_DENSE = ("iid", "repeat", "equal+", "equal-")     # families whose 62 x 4 strips overflow the parking buffer
+SIFT_EXT_BUF = 128                                       # k_extrema.hpp: candidates a wave parks before it flushes
+
+
+def detection_dogs(family, shape, seed=0):
+    """(5, H, W) float32 DoG planes of one family."""
+    rng = np.random.default_rng(1000 + seed)
+    H, W = shape
+    if family == "iid":                                   # ties everywhere, refinement moves up to the 3 / H - 3 limits
+        d = rng.integers(-4, 5, (5, H, W))
+    elif family == "blocks":                              # 3 x 3 plateaus: singular 3-D Hessians, inf / NaN steps
+        d = np.repeat(np.repeat(rng.integers(-5, 6, (5, (H + 2) // 3, (W + 2) // 3)), 3, axis=1), 3, axis=2)[:, :H, :W]
+    elif family == "repeat":                              # ties across scales, H00 = 0
+        d = np.repeat(rng.integers(-4, 5, (1, H, W)), 5, axis=0)
+    elif family in ("equal+", "equal-"):                  # every sample a candidate at the three scales: 186 per row and wave
+        d = np.full((5, H, W), 4 if family == "equal+" else -4)
+    elif family == "spikes":                              # isolated extrema on zero: val != 0
+        d = np.where(rng.random((5, H, W)) < 0.02, rng.integers(3, 9, (5, H, W)) * rng.choice([-1, 1], (5, H, W)), 0)
+    elif family == "levels":                              # the contrast threshold 0.8 * 3.4 = 2.72 from both sides
+        d = rng.choice(np.array([0.0, 2.5, -2.5, 2.75, -2.75, 3.0, -3.0]), (5, H, W))
+    elif family == "waves":                               # slanted ridges: the edge test drops a third, the two thresholds differ
+        y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+        d = np.stack([np.rint(6.0 * np.sin(0.9 * y + 0.9 * s + 0.3 * x) * np.cos(0.12 * x - 0.7 * s)) for s in range(5)])
+    elif family in ("nan", "+inf", "-inf", "mixed"):      # 60 non-finite samples in iid planes
+        d = rng.integers(-4, 5, (5, H, W)).astype(np.float32)
+        bad = {"nan": [np.nan], "+inf": [np.inf], "-inf": [-np.inf], "mixed": [np.nan, np.inf, -np.inf]}[family]
+        at = rng.choice(d.size, 60, replace=False)
+        d.ravel()[at] = np.array(bad, np.float32)[np.arange(60) % len(bad)]
+    else:
+        raise ValueError(family)
+    return np.ascontiguousarray(d, np.float32)
+
+
+def blurs_from_dogs(dogs):
+    """Six blur planes whose differences are `dogs` exactly (where finite): blur[5] = 64, blur[s] = blur[s + 1] + dog[s]."""
+    blurs = np.empty((6,) + dogs.shape[1:], np.float32)
+    blurs[5] = 64.0
+    with np.errstate(invalid="ignore"):
+        for s in range(4, -1, -1):
+            blurs[s] = blurs[s + 1] + dogs[s]
+    return blurs
+
+
+def detection_planes(family, shape, seed=0):
+    return blurs_from_dogs(detection_dogs(family, shape, seed))
+
+
+def sort_rows_bits(a):
+    """Rows sorted by their bit patterns (total order also with NaN / inf / -0 in them), returned as uint32."""
+    a = np.ascontiguousarray(a, np.float32)
+    u = a.view(np.uint32).reshape(len(a), a.shape[1] if a.ndim > 1 else 1)
+    return u[np.lexsort(u.T[::-1])]
+
+
+def detection_expected(local_maxmin, interp_keypoint, dogs, octsize, par, band=None):
+    """What the detection stage must return, from the stage functions of a judge (the oracle's, or the reference's own
+    kernels): (candidates (n, 4) of the three scales, their count per scale, refined rows (m, 5) = (peak, row, col, sigma,
+    scale)).  band = (y_lo, y_hi): only the candidates of those rows."""
+    _, H, W = dogs.shape
+    cands = []
+    for s in (1, 2, 3):
+        k, n = local_maxmin(dogs, s, octsize, H * W, par)
+        assert n <= H * W
+        k = k[:n]
+        if band is not None:
+            k = k[(k[:, 1] >= band[0]) & (k[:, 1] < band[1])]
+        cands.append(k)
+    cand = np.ascontiguousarray(np.concatenate(cands))
+    return cand, [len(k) for k in cands], refined_expected(interp_keypoint, dogs, cand, par)
+
+
+def refined_expected(interp_keypoint, dogs, cand, par):
+    """Refined rows (peak, row, col, sigma, scale) of the candidates that survive interp_keypoint (holes stay holes)."""
+    cand = np.ascontiguousarray(cand, np.float32).reshape(-1, 4)
+    if len(cand) == 0:
+        return np.empty((0, 5), np.float32)
+    interp = interp_keypoint(dogs, cand, 0, len(cand), par)
+    with np.errstate(invalid="ignore"):
+        keep = (cand[:, 1] != -1) & ~((interp[:, 0] == -1) & (interp[:, 1] == -1) & (interp[:, 2] == -1) & (interp[:, 3] == -1))
+    return np.ascontiguousarray(np.concatenate([interp[keep], cand[keep][:, 3:4]], axis=1))
+
+
+def strip_candidate_counts(cand, W, H, border, rows):
+    """(ny, nx) candidates per extrema strip -- 62 columns x `rows` rows from (border, border), the three scales together."""
+    nx, ny = (W - 2 * border + 61) // 62, (H - 2 * border + rows - 1) // rows
+    counts = np.zeros((ny, nx), np.int64)
+    np.add.at(counts, ((cand[:, 1].astype(np.int64) - border) // rows, (cand[:, 2].astype(np.int64) - border) // 62), 1)
+    return counts
