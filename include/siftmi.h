@@ -230,6 +230,23 @@ int siftmi_match_set_roi(siftmi_matcher *m, const int8_t *roi, int32_t roi_width
 int siftmi_match_ex(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t roi_mode,
                     int32_t mutual, int32_t *pairs, int64_t capacity, int64_t *n_out, int64_t *n_total);
+/* Consensus filter over the pairs of a match (no reference counterpart: the reference hands this to the third-party
+ * feature.sift_orsa, sift-src/alignment.py:54-57, 260-264).  n_hyp affine maps are solved from pseudo-random triples of matches,
+ * every match votes for every map that brings its list-1 position within `tol` pixels of its list-2 position, the map with most
+ * votes wins (ties: the smallest index) and mask[j] = 1 for its voters.  Deterministic for (inputs, n_hyp, tol, seed) and restated
+ * exactly in numpy (tests/consensus_ref.py).  A pair with an index outside its list never votes.
+ * Fewer than three pairs, or no triple with |det| >= 1: *winner = -1, the mask all zero, SIFTMI_OK.
+ * SIFTMI_EINVAL, nothing launched: n_hyp outside 1..2^20, tol not finite or not > 0, a negative count, a null list, pairs or
+ * mask with a non-zero count.
+ *   mask         host, n_pairs bytes              model      host, 6 floats (a, b, c, d, e, f): x' = a x + b y + c,
+ *   winner       index of the winning map, -1: none          y' = d x + e y + f; untouched without a winner
+ *   votes_all    optional, host, n_hyp (test hook)           models_all  optional, host, n_hyp * 6, void rows all NaN (test hook)
+ *   kernel_ms    optional: hipEvent time of the vote kernel alone */
+int siftmi_match_consensus(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                           const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
+                           const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
+                           int32_t n_hyp, float tol, uint32_t seed, uint8_t *mask, float *model, int32_t *winner,
+                           int32_t *winner_votes, int32_t *votes_all, float *models_all, double *kernel_ms);
 int siftmi_match_last_kernel_ms(const siftmi_matcher *plan, float *ms);
 /* profile != 0 at creation: device time in ms of the last call's stages, in the order of the events the reference
  * appends under profile=True (sift-src/match.py:226-263): ms4[0] "copy H->D KP_1", [1] "copy H->D KP_2", [2] "matching",

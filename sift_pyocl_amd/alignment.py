@@ -12,7 +12,9 @@ Behavioural notes (deliberate):
     ``utils.matching_correction`` stops before solving (utils.py:156-189);
   * the warp writes the whole ``outshape`` (the reference launches one work-item per *input* pixel and leaves
     the ``extra`` margin of its output undefined);
-  * ``orsa=True`` needs the third-party ``feature`` module, exactly as in the reference; absent -> warning.
+  * ``orsa=True`` needs the third-party ``feature`` module, exactly as in the reference; absent -> warning;
+  * ``robust=True`` (extension, off by default) filters the matches with ``MatchPlan.consensus`` on the device before
+    the fit: the pairs that agree on one affine map within ``robust_tol`` pixels are kept, the rest never reach it.
 """
 import ctypes as C
 import logging
@@ -221,7 +223,8 @@ class LinearAlign(object):
                 numpy.ascontiguousarray(self.relative_transfo[:2, 2], dtype=numpy.float32))
 
     # ------------------------------------------------------------------ public entry
-    def align(self, img, shift_only=False, return_all=False, double_check=False, relative=False, orsa=False):
+    def align(self, img, shift_only=False, return_all=False, double_check=False, relative=False, orsa=False,
+              robust=False, robust_tol=3.0, robust_hyp=2048):
         """Align `img` on the reference image.
 
         :param img: image to align (same shape as the reference)
@@ -230,6 +233,11 @@ class LinearAlign(object):
         :param double_check: re-fit after rejecting 4-sigma outliers in displacement, angle and scale
         :param relative: make this frame the reference of the next one and accumulate the transformations
         :param orsa: filter the matches with ``feature.sift_orsa`` when that module is importable
+        :param robust: (extension) keep only the matches that agree on one affine map (``MatchPlan.consensus`` with a fixed
+                       seed: the same list of matches gives the same mask); the estimate, ``double_check`` and ``rms`` then
+                       act on those.  ``return_all`` gains the key ``"inliers"``, the boolean mask over ``"matching"``.
+        :param robust_tol: distance in pixels within which a match agrees with a candidate map
+        :param robust_hyp: number of candidate maps tried
         :return: the aligned image, the dict, or None when no keypoint matches
         """
         logger.debug("ref_keypoints: %s" % self.ref_kp.size)
@@ -263,11 +271,25 @@ class LinearAlign(object):
 
             matching = None
             if orsa and feature is None:
-                logger.warning("feature is not available. No ORSA filtering")
+                logger.warning("feature is not available. No ORSA filtering (robust=True filters on the device)")
             elif orsa:
                 matching = feature.sift_orsa(matched_records(), self.shape, 1)
                 g0, g1 = self._xysa(numpy.ascontiguousarray(matching[:, 0])), self._xysa(numpy.ascontiguousarray(matching[:, 1]))
 
+            inliers = None
+            if robust:
+                if matching is not None:        # ORSA kept a subset: the consensus runs on the records it returned
+                    m0, m1 = numpy.ascontiguousarray(matching[:, 0]), numpy.ascontiguousarray(matching[:, 1])
+                    idx = numpy.arange(m0.shape[0], dtype=numpy.int32)
+                    found = self.match.consensus(m0, m1, numpy.stack([idx, idx], axis=1), n_hyp=robust_hyp, tol=robust_tol, seed=0)
+                else:                           # both lists are still where match() read them
+                    found = self.match.consensus(ref_list, self.sift.device_records(), pairs, n_hyp=robust_hyp, tol=robust_tol, seed=0)
+                inliers = found[0]
+                if found[1] is None:
+                    logger.warning("No consensus among %s matches: all of them are used" % g0.shape[0])
+                else:
+                    g0, g1 = g0[inliers], g1[inliers]
+                    n_pairs = g0.shape[0]
             enough = n_pairs >= MIN_MATCHES_AFFINE
             if shift_only or not enough:
                 (logger.debug if shift_only else logger.warning)("Shift Only mode: Common keypoints: %s" % n_pairs)
@@ -295,7 +317,10 @@ class LinearAlign(object):
         rms = numpy.sqrt((ry * ry + rx * rx).mean())
         if matching is None:
             matching = matched_records()
-        return {"result": result, "keypoint": kp, "matching": matching, "offset": offset, "matrix": matrix, "rms": rms}
+        out = {"result": result, "keypoint": kp, "matching": matching, "offset": offset, "matrix": matrix, "rms": rms}
+        if robust:
+            out["inliers"] = inliers
+        return out
 
     __call__ = align
 

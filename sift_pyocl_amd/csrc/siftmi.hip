@@ -26,6 +26,7 @@
 #include "k_descriptor.hpp"
 #include "k_align.hpp"
 #include "k_match.hpp"
+#include "k_consensus.hpp"
 #include "k_pyramid.hpp"
 #include "k_tail.hpp"
 #include "siftmath.hpp"
@@ -2164,6 +2165,14 @@ struct siftmi_matcher {
     int64_t cap_nearest = 0;
     int2 *pairs2 = nullptr;
     int64_t cap_pairs2 = 0;
+    // consensus filter (siftmi_match_consensus): the gathered matches, the hypotheses and their votes; grown on demand
+    float4 *c_pts = nullptr;
+    uint8_t *c_mask = nullptr, *c_valid = nullptr;
+    float *c_models = nullptr;
+    int *c_votes = nullptr;
+    int64_t cap_c_pts = 0, cap_c_mask = 0, cap_c_valid = 0, cap_c_models = 0, cap_c_votes = 0;
+    ConsensusResult *c_result = nullptr;
+    hipEvent_t ec_a = nullptr, ec_b = nullptr;
 };
 
 namespace {
@@ -2197,7 +2206,7 @@ int siftmi_match_create(int64_t size, int32_t device_id, int32_t profile, siftmi
     if (!rc) rc = ensure((void **)&m->kp2, &m->cap2, size, 144);
     if (!rc) rc = ensure((void **)&m->pairs, &m->cap_pairs, size, sizeof(int2));
     if (!rc && hipMalloc((void **)&m->counter, 16) != hipSuccess) rc = fail(SIFTMI_ENOMEM, "hipMalloc failed");
-    if (!rc) { hipEventCreate(&m->ea); hipEventCreate(&m->eb); }
+    if (!rc) { hipEventCreate(&m->ea); hipEventCreate(&m->eb); hipEventCreate(&m->ec_a); hipEventCreate(&m->ec_b); }
     if (!rc && profile) for (hipEvent_t &e : m->ev) if (hipEventCreate(&e) != hipSuccess) rc = fail(SIFTMI_EDEVICE, "hipEventCreate failed");
     if (rc) { std::string keep = g_err; siftmi_match_destroy(m); g_err = keep; return rc; }
     *out = m;
@@ -2212,8 +2221,11 @@ int siftmi_match_destroy(siftmi_matcher *m) {
     if (m->kp2) hipFree(m->kp2);
     if (m->pairs) hipFree(m->pairs);
     if (m->partial) hipFree(m->partial);
-    for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2})
+    for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
+                    (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result})
         if (q) hipFree(q);
+    if (m->ec_a) hipEventDestroy(m->ec_a);
+    if (m->ec_b) hipEventDestroy(m->ec_b);
     if (m->counter) hipFree(m->counter);
     if (m->ea) hipEventDestroy(m->ea);
     if (m->eb) hipEventDestroy(m->eb);
@@ -2367,6 +2379,91 @@ int siftmi_match(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int3
                  const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t *pairs,
                  int64_t capacity, int64_t *n_out, int64_t *n_total) {
     return siftmi_match_ex(m, kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, ratio_th, 0, 0, pairs, capacity, n_out, n_total);
+}
+
+// Consensus filter over the pairs of a match (k_consensus.hpp; the contract is DESIGN.md section 7 row 5).  The lists and the
+// pairs are used where they lie; host ones are staged in the matcher's own buffers.
+int siftmi_match_consensus(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                           const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
+                           const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
+                           int32_t n_hyp, float tol, uint32_t seed, uint8_t *mask, float *model, int32_t *winner,
+                           int32_t *winner_votes, int32_t *votes_all, float *models_all, double *kernel_ms) {
+    if (!m || !winner) return fail(SIFTMI_EINVAL, "null argument");
+    if (n1 < 0 || n2 < 0 || n_pairs < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff || n_pairs > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n_pairs > 0 && (!pairs || !mask)) return fail(SIFTMI_EINVAL, "null pairs or mask with %lld pairs", (long long)n_pairs);
+    if (n_hyp < 1 || n_hyp > (1 << 20)) return fail(SIFTMI_EINVAL, "n_hyp %d outside 1..2^20", n_hyp);
+    if (!std::isfinite(tol) || !(tol > 0.f)) return fail(SIFTMI_EINVAL, "tol must be finite and > 0");
+    HIPCHK(hipSetDevice(m->device));
+    *winner = -1;
+    if (winner_votes) *winner_votes = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (n_pairs < 3) {      // every triple repeats an index: nothing can win, nothing is launched
+        if (n_pairs > 0) memset(mask, 0, (size_t)n_pairs);
+        if (votes_all) memset(votes_all, 0, sizeof(int32_t) * (size_t)n_hyp);
+        if (models_all) for (int64_t i = 0; i < (int64_t)n_hyp * 6; i++) models_all[i] = std::nanf("");
+        return SIFTMI_OK;
+    }
+    if (kp1_is_device || kp2_is_device || pairs_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    const int2 *dp = (const int2 *)pairs;
+    int rc;
+    if (!kp1_is_device && n1 > 0) {
+        if ((rc = ensure((void **)&m->kp1, &m->cap1, n1, 144))) return rc;
+        HIPCHK(hipMemcpyAsync(m->kp1, kp1, (size_t)n1 * 144, hipMemcpyHostToDevice, m->stream));
+        d1 = m->kp1;
+    }
+    if (!kp2_is_device && n2 > 0) {
+        if ((rc = ensure((void **)&m->kp2, &m->cap2, n2, 144))) return rc;
+        HIPCHK(hipMemcpyAsync(m->kp2, kp2, (size_t)n2 * 144, hipMemcpyHostToDevice, m->stream));
+        d2 = m->kp2;
+    }
+    if (!pairs_is_device) {
+        if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, n_pairs, sizeof(int2)))) return rc;
+        HIPCHK(hipMemcpyAsync(m->pairs, pairs, (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, m->stream));
+        dp = m->pairs;
+    }
+    if ((rc = ensure((void **)&m->c_pts, &m->cap_c_pts, n_pairs, sizeof(float4))) ||
+        (rc = ensure((void **)&m->c_mask, &m->cap_c_mask, n_pairs, 1)) ||
+        (rc = ensure((void **)&m->c_valid, &m->cap_c_valid, n_hyp, 1)) ||
+        (rc = ensure((void **)&m->c_models, &m->cap_c_models, (int64_t)n_hyp * 6, sizeof(float))) ||
+        (rc = ensure((void **)&m->c_votes, &m->cap_c_votes, n_hyp, sizeof(int)))) return rc;
+    if (!m->c_result) HIPCHK(hipMalloc((void **)&m->c_result, sizeof(ConsensusResult)));
+    const int M = (int)n_pairs, H = n_hyp;
+    const float tol2 = tol * tol;
+    const unsigned mblocks = (unsigned)((M + 255) / 256);
+    hipLaunchKernelGGL(consensus_gather_kernel, dim3(mblocks), dim3(256), 0, m->stream, d1, (int)n1, d2, (int)n2, dp, M, m->c_pts);
+    hipLaunchKernelGGL(consensus_solve_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, m->stream, (const float4 *)m->c_pts,
+                       (uint32_t)M, H, seed, m->c_models, m->c_valid, m->c_votes);
+    // vote grid: tiles of matches x chunks of hypotheses, about eight workgroups per CU; a chunk is at most the kernel's LDS counters
+    // and at least 16 hypotheses (a workgroup's loads of its matches must be worth its walk)
+    const int tiles = (M + SIFT_CONS_TILE - 1) / SIFT_CONS_TILE;
+    int chunks = (2048 + tiles - 1) / tiles;
+    const int min_chunks = (H + SIFT_CONS_HMAX - 1) / SIFT_CONS_HMAX, max_chunks = (H + 15) / 16;
+    if (chunks > max_chunks) chunks = max_chunks;
+    if (chunks < min_chunks) chunks = min_chunks;
+    const int h_chunk = (H + chunks - 1) / chunks;
+    chunks = (H + h_chunk - 1) / h_chunk;
+    hipEventRecord(m->ec_a, m->stream);
+    hipLaunchKernelGGL(consensus_vote_kernel, dim3((unsigned)tiles, (unsigned)chunks), dim3(SIFT_CONS_THREADS), 0, m->stream,
+                       (const float4 *)m->c_pts, M, (const float *)m->c_models, H, h_chunk, tol2, m->c_votes);
+    hipEventRecord(m->ec_b, m->stream);
+    hipLaunchKernelGGL(consensus_select_kernel, dim3(1), dim3(256), 0, m->stream, (const int *)m->c_votes, (const uint8_t *)m->c_valid,
+                       (const float *)m->c_models, H, m->c_result);
+    hipLaunchKernelGGL(consensus_mask_kernel, dim3(mblocks), dim3(256), 0, m->stream, (const float4 *)m->c_pts, M,
+                       (const ConsensusResult *)m->c_result, tol2, m->c_mask);
+    ConsensusResult res;
+    HIPCHK(hipMemcpyAsync(&res, m->c_result, sizeof res, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(mask, m->c_mask, (size_t)M, hipMemcpyDeviceToHost, m->stream));
+    if (votes_all) HIPCHK(hipMemcpyAsync(votes_all, m->c_votes, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, m->stream));
+    if (models_all) HIPCHK(hipMemcpyAsync(models_all, m->c_models, sizeof(float) * 6 * (size_t)H, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
+    *winner = res.winner;
+    if (winner_votes) *winner_votes = res.votes;
+    if (res.winner >= 0 && model) memcpy(model, res.model, sizeof res.model);
+    return SIFTMI_OK;
 }
 
 int siftmi_match_last_kernel_ms(const siftmi_matcher *m, float *ms) {

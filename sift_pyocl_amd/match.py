@@ -114,6 +114,42 @@ class MatchPlan(object):
 
     __call__ = match
 
+    def consensus(self, kp1, kp2, pairs, n_hyp=2048, tol=3.0, seed=0, return_votes=False):
+        """Tell the pairs of a ``match(..., raw_results=True)`` that agree on one affine map from the rest (extension; the
+        reference's ``orsa=True`` needs the third-party ``feature`` module).  ``n_hyp`` maps are solved from pseudo-random
+        triples of pairs, every pair votes for every map that brings its ``kp1`` position within ``tol`` pixels of its ``kp2``
+        position, and the map with most votes wins.  Deterministic for given inputs, ``n_hyp``, ``tol`` and ``seed``
+        (DESIGN.md section 7 row 5 is the exact arithmetic).
+
+        :param kp1, kp2: the keypoint lists ``pairs`` indexes, numpy records or device tensors as for ``match``
+        :param pairs: (M, 2) int32 indices, a numpy array or a device tensor
+        :return: ``(mask, model, votes)``: bool (M,) voters of the winning map, its float32 (a, b, c, d, e, f) with
+                 x' = a x + b y + c, y' = d x + e y + f (``utils.affine_least_squares`` order; None when no triple is
+                 usable, the mask is then all False) and its vote count; with ``return_votes`` a fourth item
+                 ``(votes_all, models_all)``: int32 (n_hyp,), float32 (n_hyp, 6) with unusable triples as NaN rows
+        """
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        pp, devp, pdtype, pshape, keepp = _pointer_of(pairs)
+        if pdtype != numpy.int32 or len(pshape) != 2 or pshape[1] != 2:
+            raise RuntimeError("pairs must be an (M, 2) int32 array")
+        n_pairs, n_hyp = int(pshape[0]), int(n_hyp)
+        mask = numpy.zeros(n_pairs, numpy.uint8)
+        model = numpy.zeros(6, numpy.float32)
+        votes_all = numpy.zeros(max(n_hyp, 0), numpy.int32) if return_votes else None
+        models_all = numpy.zeros((max(n_hyp, 0), 6), numpy.float32) if return_votes else None
+        winner, votes, ms = C.c_int32(-1), C.c_int32(0), C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_consensus(
+                self._handle, p1, n1, dev1, p2, n2, dev2, pp if n_pairs else None, n_pairs, devp, n_hyp, C.c_float(tol),
+                int(seed) & 0xFFFFFFFF, mask.ctypes.data, model.ctypes.data, C.byref(winner), C.byref(votes),
+                votes_all.ctypes.data if return_votes else None, models_all.ctypes.data if return_votes else None, C.byref(ms)))
+            if self.profile:
+                from .plan import StageEvent
+                self.events.append(("consensus", StageEvent(ms.value)))      # device time of the vote kernel
+        result = (mask.view(numpy.bool_), model if winner.value >= 0 else None, int(votes.value))
+        return result + ((votes_all, models_all),) if return_votes else result
+
     def _records(self, kp):
         if isinstance(kp, numpy.ndarray):
             arr = numpy.ascontiguousarray(kp)
