@@ -1,0 +1,347 @@
+// match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp) and the consensus filter over its
+// pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "host_common.hpp"
+#include "k_match.hpp"
+#include "k_consensus.hpp"
+
+using namespace siftk;
+
+struct siftmi_matcher {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int64_t size = 0;
+    int profile = 0;
+    uint8_t *kp1 = nullptr, *kp2 = nullptr;
+    int64_t cap1 = 0, cap2 = 0;
+    int2 *pairs = nullptr;
+    int64_t cap_pairs = 0;
+    MatchPartial *partial = nullptr;
+    int64_t cap_partial = 0;
+    int *counter = nullptr;
+    hipEvent_t ea = nullptr, eb = nullptr;
+    float last_ms = 0;
+    // profile != 0: the events of match.py:226-263 -- "copy H->D KP_1", "copy H->D KP_2", "matching", "copy D->H match" -- as
+    // device times of the last call in ms (-1: the stage did not run: a device-resident list, no pair to copy)
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float stage_ms[4] = {-1.f, -1.f, -1.f, -1.f};
+    // ROI mask (MatchPlan.set_roi, match.py:312-320) and the scratch of the masked / mutual variants
+    int8_t *roi = nullptr;
+    int64_t cap_roi = 0;
+    int roi_w = 0, roi_h = 0;
+    uint8_t *q1 = nullptr, *l1 = nullptr, *q2 = nullptr, *l2 = nullptr;   // per-keypoint flags (as query / as list element)
+    int64_t cap_q1 = 0, cap_l1 = 0, cap_q2 = 0, cap_l2 = 0;
+    int *nearest = nullptr;
+    int64_t cap_nearest = 0;
+    int2 *pairs2 = nullptr;
+    int64_t cap_pairs2 = 0;
+    // consensus filter (siftmi_match_consensus): the gathered matches, the hypotheses and their votes; grown on demand
+    float4 *c_pts = nullptr;
+    uint8_t *c_mask = nullptr, *c_valid = nullptr;
+    float *c_models = nullptr;
+    int *c_votes = nullptr;
+    int64_t cap_c_pts = 0, cap_c_mask = 0, cap_c_valid = 0, cap_c_models = 0, cap_c_votes = 0;
+    ConsensusResult *c_result = nullptr;
+    hipEvent_t ec_a = nullptr, ec_b = nullptr;
+};
+
+namespace {
+int ensure(void **ptr, int64_t *cap, int64_t need, size_t elem) {
+    if (need <= *cap && *ptr) return SIFTMI_OK;
+    if (*ptr) hipFree(*ptr);
+    *ptr = nullptr; *cap = 0;
+    hipError_t e = hipMalloc(ptr, (size_t)(need > 0 ? need : 1) * elem);
+    if (e != hipSuccess) return fail(SIFTMI_ENOMEM, "hipMalloc(%lld x %zu): %s", (long long)need, elem, hipGetErrorString(e));
+    *cap = need;
+    return SIFTMI_OK;
+}
+// a host list of n records is staged in the matcher's own buffer (*d then points there); a device list is used where it lies
+int stage_list(siftmi_matcher *m, uint8_t **buf, int64_t *cap, const siftmi_keypoint *kp, int64_t n, const uint8_t **d) {
+    int rc = ensure((void **)buf, cap, n, 144);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(*buf, kp, (size_t)n * 144, hipMemcpyHostToDevice, m->stream));
+    *d = *buf;
+    return SIFTMI_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int siftmi_match_create(int64_t size, int32_t device_id, int32_t profile, siftmi_matcher **out) {
+    if (!out) return fail(SIFTMI_EINVAL, "null argument");
+    *out = nullptr;
+    if (size < 1) return fail(SIFTMI_EINVAL, "size must be >= 1");
+    int ndev = siftmi_device_count();
+    if (ndev < 1) return fail(SIFTMI_EDEVICE, "no HIP device available");
+    if (device_id < 0 || device_id >= ndev) return fail(SIFTMI_EINVAL, "device %d out of range", device_id);
+    HIPCHK(hipSetDevice(device_id));
+    siftmi_matcher *m = new (std::nothrow) siftmi_matcher();
+    if (!m) return fail(SIFTMI_ENOMEM, "host allocation failed");
+    m->device = device_id; m->size = size; m->profile = profile;
+    int rc = SIFTMI_OK;
+    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(SIFTMI_EDEVICE, "hipStreamCreate failed");
+    if (!rc) rc = ensure((void **)&m->kp1, &m->cap1, size, 144);
+    if (!rc) rc = ensure((void **)&m->kp2, &m->cap2, size, 144);
+    if (!rc) rc = ensure((void **)&m->pairs, &m->cap_pairs, size, sizeof(int2));
+    if (!rc && hipMalloc((void **)&m->counter, 16) != hipSuccess) rc = fail(SIFTMI_ENOMEM, "hipMalloc failed");
+    if (!rc) { hipEventCreate(&m->ea); hipEventCreate(&m->eb); hipEventCreate(&m->ec_a); hipEventCreate(&m->ec_b); }
+    if (!rc && profile) for (hipEvent_t &e : m->ev) if (hipEventCreate(&e) != hipSuccess) rc = fail(SIFTMI_EDEVICE, "hipEventCreate failed");
+    if (rc) { std::string keep = g_err; siftmi_match_destroy(m); g_err = keep; return rc; }
+    *out = m;
+    return SIFTMI_OK;
+}
+
+int siftmi_match_destroy(siftmi_matcher *m) {
+    if (!m) return SIFTMI_OK;
+    hipSetDevice(m->device);
+    if (m->stream) hipStreamSynchronize(m->stream);
+    if (m->kp1) hipFree(m->kp1);
+    if (m->kp2) hipFree(m->kp2);
+    if (m->pairs) hipFree(m->pairs);
+    if (m->partial) hipFree(m->partial);
+    for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
+                    (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result})
+        if (q) hipFree(q);
+    if (m->ec_a) hipEventDestroy(m->ec_a);
+    if (m->ec_b) hipEventDestroy(m->ec_b);
+    if (m->counter) hipFree(m->counter);
+    if (m->ea) hipEventDestroy(m->ea);
+    if (m->eb) hipEventDestroy(m->eb);
+    for (hipEvent_t e : m->ev) if (e) hipEventDestroy(e);
+    if (m->stream) hipStreamDestroy(m->stream);
+    delete m;
+    return SIFTMI_OK;
+}
+
+int siftmi_match_set_roi(siftmi_matcher *m, const int8_t *roi, int32_t roi_width, int32_t roi_height) {
+    if (!m) return fail(SIFTMI_EINVAL, "null matcher");
+    HIPCHK(hipSetDevice(m->device));
+    if (!roi) { m->roi_w = m->roi_h = 0; return SIFTMI_OK; }       // unset_roi
+    if (roi_width < 1 || roi_height < 1) return fail(SIFTMI_EINVAL, "bad ROI shape %d x %d", roi_width, roi_height);
+    int rc = ensure((void **)&m->roi, &m->cap_roi, (int64_t)roi_width * roi_height, 1);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(m->roi, roi, (size_t)roi_width * roi_height, hipMemcpyHostToDevice));
+    m->roi_w = roi_width; m->roi_h = roi_height;
+    return SIFTMI_OK;
+}
+
+namespace {
+// one direction of the brute-force scan: partials of `nq` queries against `nl` list elements, folded by the merge kernel
+int match_direction(siftmi_matcher *m, const uint8_t *dq, int64_t nq, const uint8_t *dl, int64_t nl, const uint8_t *qflag,
+                    const uint8_t *lflag, float ratio_th, int2 *pairs, int cap, int *nearest) {
+    // 2-D decomposition: query blocks x partitions of the list, enough workgroups to fill 256 CUs
+    const int qblocks = (int)((nq + 256 * SIFT_MATCH_QPT - 1) / (256 * SIFT_MATCH_QPT));
+    int nparts = (2048 + qblocks - 1) / qblocks;
+    const int max_parts = (int)((nl + 4 * SIFT_MATCH_TILE - 1) / (4 * SIFT_MATCH_TILE));
+    if (nparts > max_parts) nparts = max_parts;
+    const int min_parts = (int)((nl + SIFT_MATCH_MAX_PART - 1) / SIFT_MATCH_MAX_PART);     // 16-bit index inside a partition
+    if (nparts < min_parts) nparts = min_parts;
+    if (nparts < 1) nparts = 1;
+    int part_len = (int)((nl + nparts - 1) / nparts);
+    part_len = (part_len + SIFT_MATCH_TILE - 1) / SIFT_MATCH_TILE * SIFT_MATCH_TILE;
+    nparts = (int)((nl + part_len - 1) / part_len);
+    int rc;
+    if ((rc = ensure((void **)&m->partial, &m->cap_partial, (int64_t)nparts * nq, sizeof(MatchPartial)))) return rc;
+    const dim3 grid((unsigned)qblocks, (unsigned)nparts);
+    if (lflag)
+        hipLaunchKernelGGL(match_partial_kernel<true>, grid, dim3(256), 0, m->stream, dq, (int)nq, dl, (int)nl, part_len, m->partial, qflag, lflag);
+    else
+        hipLaunchKernelGGL(match_partial_kernel<false>, grid, dim3(256), 0, m->stream, dq, (int)nq, dl, (int)nl, part_len, m->partial,
+                           (const uint8_t *)nullptr, (const uint8_t *)nullptr);
+    hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, m->stream,
+                       (const MatchPartial *)m->partial, (int)nq, nparts, ratio_th, pairs, m->counter, cap, qflag, nearest);
+    return SIFTMI_OK;
+}
+}  // namespace
+
+int siftmi_match_ex(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                    const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t roi_mode,
+                    int32_t mutual, int32_t *pairs, int64_t capacity, int64_t *n_out, int64_t *n_total) {
+    if (!m || !n_out) return fail(SIFTMI_EINVAL, "null argument");
+    if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (roi_mode < 0 || roi_mode > 2) return fail(SIFTMI_EINVAL, "roi_mode must be 0 (off), 1 (matching_valid) or 2 (strict)");
+    if (roi_mode && !(m->roi && m->roi_w > 0)) return fail(SIFTMI_EINVAL, "roi_mode %d without a region of interest (siftmi_match_set_roi)", roi_mode);
+    HIPCHK(hipSetDevice(m->device));
+    *n_out = 0;
+    if (n_total) *n_total = 0;
+    for (float &v : m->stage_ms) v = -1.f;
+    if (n1 == 0 || n2 == 0) return SIFTMI_OK;   // dist1 == dist2 == 1e12 -> ratio 1, never < ratio_th
+    if (kp1_is_device || kp2_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    int rc;
+    const bool prof = m->profile && m->ev[0];
+    if (prof) hipEventRecord(m->ev[0], m->stream);
+    if (!kp1_is_device && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (prof) hipEventRecord(m->ev[1], m->stream);
+    if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (prof) hipEventRecord(m->ev[2], m->stream);
+    // match.py:241-243,252: output capacity = max(self.kpsize, min(n1, n2))
+    int64_t cap = m->size;
+    if ((n1 < n2 ? n1 : n2) > cap) cap = (n1 < n2 ? n1 : n2);
+    if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, cap, sizeof(int2)))) return rc;
+    HIPCHK(hipMemsetAsync(m->counter, 0, 8, m->stream));
+    hipEventRecord(m->ea, m->stream);
+    const uint8_t *qf1 = nullptr, *lf2 = nullptr;
+    if (roi_mode) {
+        if ((rc = ensure((void **)&m->q1, &m->cap_q1, n1, 1)) || (rc = ensure((void **)&m->l1, &m->cap_l1, n1, 1)) ||
+            (rc = ensure((void **)&m->q2, &m->cap_q2, n2, 1)) || (rc = ensure((void **)&m->l2, &m->cap_l2, n2, 1))) return rc;
+        hipLaunchKernelGGL(match_roi_flags_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, d1, (int)n1,
+                           (const int8_t *)m->roi, m->roi_w, m->roi_h, roi_mode, m->q1, m->l1);
+        hipLaunchKernelGGL(match_roi_flags_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, m->stream, d2, (int)n2,
+                           (const int8_t *)m->roi, m->roi_w, m->roi_h, roi_mode, m->q2, m->l2);
+        qf1 = m->q1; lf2 = m->l2;
+    }
+    if ((rc = match_direction(m, d1, n1, d2, n2, qf1, lf2, ratio_th, m->pairs, (int)cap, nullptr))) return rc;
+    int2 *result = m->pairs;
+    int *result_counter = m->counter;
+    int count = 0;
+    if (mutual) {
+        // reverse scan: nearest list-1 keypoint of every list-2 keypoint over the same masked distances
+        if ((rc = ensure((void **)&m->nearest, &m->cap_nearest, n2, sizeof(int))) ||
+            (rc = ensure((void **)&m->pairs2, &m->cap_pairs2, cap, sizeof(int2)))) return rc;
+        const uint8_t *qf2 = nullptr, *lf1 = nullptr;
+        if (roi_mode) {
+            hipLaunchKernelGGL(match_reverse_flags_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, m->stream, (const uint8_t *)m->l2, (int)n2, m->q2);
+            hipLaunchKernelGGL(match_reverse_list_flags_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, (const uint8_t *)m->q1, (int)n1, m->l1);
+            qf2 = m->q2; lf1 = m->l1;
+        }
+        HIPCHK(hipMemcpyAsync(&count, m->counter, 4, hipMemcpyDeviceToHost, m->stream));   // forward count (the partial buffer is reused below)
+        if ((rc = match_direction(m, d2, n2, d1, n1, qf2, lf1, ratio_th, nullptr, 0, m->nearest))) return rc;
+        HIPCHK(hipStreamSynchronize(m->stream));
+        const int nfwd = count < cap ? count : (int)cap;
+        if (nfwd > 0)
+            hipLaunchKernelGGL(match_mutual_filter_kernel, dim3((unsigned)((nfwd + 255) / 256)), dim3(256), 0, m->stream,
+                               (const int2 *)m->pairs, nfwd, (const int *)m->nearest, m->pairs2, m->counter + 1);
+        result = m->pairs2; result_counter = m->counter + 1;
+    }
+    hipEventRecord(m->eb, m->stream);
+    HIPCHK(hipMemcpyAsync(&count, result_counter, 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    hipEventElapsedTime(&m->last_ms, m->ea, m->eb);
+    if (n_total) *n_total = count;
+    int64_t n = count < cap ? count : cap;
+    rc = SIFTMI_OK;
+    if (n > capacity) { n = capacity; rc = SIFTMI_ECAPACITY; g_err = "pair capacity too small; result truncated"; }
+    if (prof) {
+        m->stage_ms[2] = m->last_ms;
+        if (!kp1_is_device) hipEventElapsedTime(&m->stage_ms[0], m->ev[0], m->ev[1]);
+        if (!kp2_is_device) hipEventElapsedTime(&m->stage_ms[1], m->ev[1], m->ev[2]);
+    }
+    if (n > 0) {
+        if (!pairs) return fail(SIFTMI_EINVAL, "null pairs buffer");
+        if (prof) {
+            hipEventRecord(m->ev[3], m->stream);
+            HIPCHK(hipMemcpyAsync(pairs, result, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost, m->stream));
+            hipEventRecord(m->ev[4], m->stream);
+            HIPCHK(hipStreamSynchronize(m->stream));
+            hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
+        } else {
+            HIPCHK(hipMemcpy(pairs, result, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+        }
+    }
+    *n_out = n;
+    return rc;
+}
+
+int siftmi_match(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                 const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t *pairs,
+                 int64_t capacity, int64_t *n_out, int64_t *n_total) {
+    return siftmi_match_ex(m, kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, ratio_th, 0, 0, pairs, capacity, n_out, n_total);
+}
+
+// Consensus filter over the pairs of a match (k_consensus.hpp; the contract is DESIGN.md section 7 row 5).  The lists and the
+// pairs are used where they lie; host ones are staged in the matcher's own buffers.
+int siftmi_match_consensus(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                           const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
+                           const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
+                           int32_t n_hyp, float tol, uint32_t seed, uint8_t *mask, float *model, int32_t *winner,
+                           int32_t *winner_votes, int32_t *votes_all, float *models_all, double *kernel_ms) {
+    if (!m || !winner) return fail(SIFTMI_EINVAL, "null argument");
+    if (n1 < 0 || n2 < 0 || n_pairs < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff || n_pairs > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n_pairs > 0 && (!pairs || !mask)) return fail(SIFTMI_EINVAL, "null pairs or mask with %lld pairs", (long long)n_pairs);
+    if (n_hyp < 1 || n_hyp > (1 << 20)) return fail(SIFTMI_EINVAL, "n_hyp %d outside 1..2^20", n_hyp);
+    if (!std::isfinite(tol) || !(tol > 0.f)) return fail(SIFTMI_EINVAL, "tol must be finite and > 0");
+    HIPCHK(hipSetDevice(m->device));
+    *winner = -1;
+    if (winner_votes) *winner_votes = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (n_pairs < 3) {      // every triple repeats an index: nothing can win, nothing is launched
+        if (n_pairs > 0) memset(mask, 0, (size_t)n_pairs);
+        if (votes_all) memset(votes_all, 0, sizeof(int32_t) * (size_t)n_hyp);
+        if (models_all) for (int64_t i = 0; i < (int64_t)n_hyp * 6; i++) models_all[i] = std::nanf("");
+        return SIFTMI_OK;
+    }
+    if (kp1_is_device || kp2_is_device || pairs_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    const int2 *dp = (const int2 *)pairs;
+    int rc;
+    if (!kp1_is_device && n1 > 0 && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (!kp2_is_device && n2 > 0 && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (!pairs_is_device) {
+        if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, n_pairs, sizeof(int2)))) return rc;
+        HIPCHK(hipMemcpyAsync(m->pairs, pairs, (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, m->stream));
+        dp = m->pairs;
+    }
+    if ((rc = ensure((void **)&m->c_pts, &m->cap_c_pts, n_pairs, sizeof(float4))) ||
+        (rc = ensure((void **)&m->c_mask, &m->cap_c_mask, n_pairs, 1)) ||
+        (rc = ensure((void **)&m->c_valid, &m->cap_c_valid, n_hyp, 1)) ||
+        (rc = ensure((void **)&m->c_models, &m->cap_c_models, (int64_t)n_hyp * 6, sizeof(float))) ||
+        (rc = ensure((void **)&m->c_votes, &m->cap_c_votes, n_hyp, sizeof(int)))) return rc;
+    if (!m->c_result) HIPCHK(hipMalloc((void **)&m->c_result, sizeof(ConsensusResult)));
+    const int M = (int)n_pairs, H = n_hyp;
+    const float tol2 = tol * tol;
+    const unsigned mblocks = (unsigned)((M + 255) / 256);
+    hipLaunchKernelGGL(consensus_gather_kernel, dim3(mblocks), dim3(256), 0, m->stream, d1, (int)n1, d2, (int)n2, dp, M, m->c_pts);
+    hipLaunchKernelGGL(consensus_solve_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, m->stream, (const float4 *)m->c_pts,
+                       (uint32_t)M, H, seed, m->c_models, m->c_valid, m->c_votes);
+    // vote grid: tiles of matches x chunks of hypotheses, about eight workgroups per CU; a chunk is at most the kernel's LDS counters
+    // and at least 16 hypotheses (a workgroup's loads of its matches must be worth its walk)
+    const int tiles = (M + SIFT_CONS_TILE - 1) / SIFT_CONS_TILE;
+    int chunks = (2048 + tiles - 1) / tiles;
+    const int min_chunks = (H + SIFT_CONS_HMAX - 1) / SIFT_CONS_HMAX, max_chunks = (H + 15) / 16;
+    if (chunks > max_chunks) chunks = max_chunks;
+    if (chunks < min_chunks) chunks = min_chunks;
+    const int h_chunk = (H + chunks - 1) / chunks;
+    chunks = (H + h_chunk - 1) / h_chunk;
+    hipEventRecord(m->ec_a, m->stream);
+    hipLaunchKernelGGL(consensus_vote_kernel, dim3((unsigned)tiles, (unsigned)chunks), dim3(SIFT_CONS_THREADS), 0, m->stream,
+                       (const float4 *)m->c_pts, M, (const float *)m->c_models, H, h_chunk, tol2, m->c_votes);
+    hipEventRecord(m->ec_b, m->stream);
+    hipLaunchKernelGGL(consensus_select_kernel, dim3(1), dim3(256), 0, m->stream, (const int *)m->c_votes, (const uint8_t *)m->c_valid,
+                       (const float *)m->c_models, H, m->c_result);
+    hipLaunchKernelGGL(consensus_mask_kernel, dim3(mblocks), dim3(256), 0, m->stream, (const float4 *)m->c_pts, M,
+                       (const ConsensusResult *)m->c_result, tol2, m->c_mask);
+    ConsensusResult res;
+    HIPCHK(hipMemcpyAsync(&res, m->c_result, sizeof res, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(mask, m->c_mask, (size_t)M, hipMemcpyDeviceToHost, m->stream));
+    if (votes_all) HIPCHK(hipMemcpyAsync(votes_all, m->c_votes, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, m->stream));
+    if (models_all) HIPCHK(hipMemcpyAsync(models_all, m->c_models, sizeof(float) * 6 * (size_t)H, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
+    *winner = res.winner;
+    if (winner_votes) *winner_votes = res.votes;
+    if (res.winner >= 0 && model) memcpy(model, res.model, sizeof res.model);
+    return SIFTMI_OK;
+}
+
+int siftmi_match_last_kernel_ms(const siftmi_matcher *m, float *ms) {
+    if (!m || !ms) return fail(SIFTMI_EINVAL, "null argument");
+    *ms = m->last_ms;
+    return SIFTMI_OK;
+}
+
+int siftmi_match_last_stage_ms(const siftmi_matcher *m, float *ms4) {
+    if (!m || !ms4) return fail(SIFTMI_EINVAL, "null argument");
+    if (!m->profile) return fail(SIFTMI_EINVAL, "the matcher was created without profiling");
+    for (int i = 0; i < 4; i++) ms4[i] = m->stage_ms[i];
+    return SIFTMI_OK;
+}
+
+}  // extern "C"

@@ -8,25 +8,20 @@
 #include <hip/hip_ext.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <chrono>
 #include <mutex>
 #include <new>
-#include <unordered_map>
 #include <string>
 #include <vector>
 
-#include "../../include/siftmi.h"
+#include "host_common.hpp"
 #include "k_extrema.hpp"
 #include "k_keypoint.hpp"
 #include "k_descriptor.hpp"
 #include "k_align.hpp"
-#include "k_match.hpp"
-#include "k_consensus.hpp"
 #include "k_pyramid.hpp"
 #include "k_tail.hpp"
 #include "siftmath.hpp"
@@ -36,8 +31,6 @@ using namespace siftk;
 static_assert(sizeof(siftmi_keypoint) == 144, "siftmi_keypoint must be 144 bytes");
 
 namespace {
-
-thread_local std::string g_err;
 
 // Events that order one stream of a plan behind another ON THE SAME DEVICE, kernel to kernel: no timing, and no system-scope fence when they are
 // recorded.  INVARIANT: producer and consumer of such an event are kernels on this device (ev_pyr, ev_p3, ev_maps0).  Anything whose
@@ -49,23 +42,6 @@ thread_local std::string g_err;
 #endif
 #define SIFTMI_ETAILRETRY (-100)   // internal: plan_wait -> siftmi_plan_keypoints, never returned through the C ABI
 #define SIFTMI_EGROW (-101)        // internal, likewise: a list was grown, the image has to run again
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? SIFTMI_ENOMEM : SIFTMI_EDEVICE, "%s: %s", #expr, \
-                        hipGetErrorString(e_));                                                \
-    } while (0)
 
 // ---- Gaussian taps on the host: gaussian.cl:56-140 run as one work-group of nextpower(size)
 // items (plan.py:321-330); LDS tree sum restated serially in the same association order.
@@ -110,7 +86,8 @@ struct Options {
     int overlap = 1;         // detection / description streams beside the pyramid stream (0: one stream)
     int march = 1;           // marching blur for large planes (0: tiled blur everywhere)
     int small_blur = 2;      // planes below the marching cross-over with symmetric odd taps: 0 the 32 x 16 tile kernel (blur_hv_kernel),
-                             // 1 the 32 x 32 / 32 x 64 tile kernel (blur_tile2_kernel), 2 by plane size (tile2_plane)
+                             // 1 the 32 x 32 / 32 x 64 tile kernel (blur_tile2_kernel), 2 by plane size (tile2_plane).  No option name:
+                             // siftmi_plan_set_option does not know it, only siftmi_stage_blur_ex sets it (bits 2-3 of its xcd_map)
     int march_wgs = 0;       // workgroups wanted by the marching blur (0: 1024, 768 for 27 taps)
     int xcd_map = 1;         // marching blur: whole segment rows per XCD (k_pyramid.hpp: the strips' halo columns become L2 hits)
     int march_prio = 1;      // marching blur: wave priority falls by one level per quarter of a workgroup's march, so that the workgroups of a CU
@@ -339,20 +316,6 @@ inline void launch_ev(hipEvent_t stop, K kernel, dim3 grid, dim3 block, size_t l
     else hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
 }
 
-template <int N, bool NORM, int DT, int TX, int TY, int VR>
-void launch_blur_geom(hipStream_t st, const void *in, float *out, int W, int H, const TapsArg<N> &ta, const uint32_t *mm, float *half, hipEvent_t stop = nullptr) {
-    using G = BlurGeom<N, TX, TY>;
-    dim3 grid((unsigned)((W + TX - 1) / TX), (unsigned)((H + TY - 1) / TY));
-    launch_ev(stop, blur_hv_kernel<N, NORM, DT, TX, TY, VR>, grid, dim3(256), (size_t)G::LDS_BYTES, st, in, out, W, H, ta, mm, half);
-}
-
-template <int N, bool NORM, int DT, int TX, int TY>
-void launch_tile2(hipStream_t st, const void *in, float *out, int W, int H, const TapsArg<N> &ta, const uint32_t *mm, float *half, hipEvent_t stop) {
-    using G = Tile2Geom<N, TX, TY>;
-    dim3 grid((unsigned)((W + TX - 1) / TX), (unsigned)((H + TY - 1) / TY));
-    launch_ev(stop, blur_tile2_kernel<N, NORM, DT, TX, TY>, grid, dim3(256), (size_t)G::LDS_BYTES, st, in, out, W, H, ta, mm, half);
-}
-
 // Which kernel ran a blur (the stage entry point reports it): none (no fused instance for the tap count), the 32 x 16 tile
 // kernel, the marching team kernel, the small-plane tile kernel (blur_tile2_kernel).
 enum BlurForm { BLUR_NONE = 0, BLUR_TILE = 1, BLUR_TEAM = 2, BLUR_TILE2 = 3 };
@@ -376,12 +339,15 @@ BlurForm launch_blur_t(const Options &opt, hipStream_t st, const void *in, float
                        const uint32_t *mm, float *half = nullptr, hipEvent_t stop = nullptr) {
     TapsArg<N> ta;
     for (int i = 0; i < N; i++) ta.t[i] = taps[i];
+    auto tiles = [&](auto kernel, int TX, int TY, size_t lds) {      // one workgroup per TX x TY tile
+        launch_ev(stop, kernel, dim3((unsigned)((W + TX - 1) / TX), (unsigned)((H + TY - 1) / TY)), dim3(256), lds, st, in, out, W, H, ta, mm, half);
+    };
     if (tile2_plane(opt, W, H, symmetric)) {
-        if ((int64_t)W * H >= TILE2_TALL_PIXELS) launch_tile2<N, NORM, DT, 32, 64>(st, in, out, W, H, ta, mm, half, stop);
-        else launch_tile2<N, NORM, DT, 32, 32>(st, in, out, W, H, ta, mm, half, stop);
+        if ((int64_t)W * H >= TILE2_TALL_PIXELS) tiles(blur_tile2_kernel<N, NORM, DT, 32, 64>, 32, 64, Tile2Geom<N, 32, 64>::LDS_BYTES);
+        else tiles(blur_tile2_kernel<N, NORM, DT, 32, 32>, 32, 32, Tile2Geom<N, 32, 32>::LDS_BYTES);
         return BLUR_TILE2;
     }
-    launch_blur_geom<N, NORM, DT, 32, 16, 4>(st, in, out, W, H, ta, mm, half, stop);
+    tiles(blur_hv_kernel<N, NORM, DT, 32, 16, 4>, 32, 16, BlurGeom<N, 32, 16>::LDS_BYTES);
     return BLUR_TILE;
 }
 
@@ -442,34 +408,29 @@ bool taps_symmetric(const Taps &t) {
     return symmetric;
 }
 
+// One fused blur of N taps: the marching team kernel for the large planes (symmetric taps, option "march"), else a tile kernel.
+template <int N, bool NORM, int DT = 0>
+BlurForm launch_blur_n(const Options &opt, hipStream_t st, const void *in, float *out, int W, int H, const Taps &t, const uint32_t *mm, float *half = nullptr, hipEvent_t stop = nullptr) {
+    const bool symmetric = taps_symmetric(t);
+    if (march_plane(W, H) && symmetric && opt.march) { launch_march_t<N, NORM, DT>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM; }
+    return launch_blur_t<N, NORM, DT>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+}
+
 // returns the kernel launched (BlurForm; BLUR_NONE when no fused instantiation exists for this tap count).  Every fused form
 // writes `half` when it is not null.
 template <bool NORM>
 BlurForm launch_blur_tiled(const Options &opt, hipStream_t st, const float *in, float *out, int W, int H, const Taps &t, const uint32_t *mm, float *half = nullptr, hipEvent_t stop = nullptr) {
-    const bool symmetric = taps_symmetric(t);
     if constexpr (NORM) {
         // The normalising form exists for the default initial kernel only (15 taps, init_sigma = 1.6); any other
         // InitSigma sends its ONE initial blur through the generic two-pass path (BLUR_NONE).
-        if (t.n != 15) return BLUR_NONE;
-        if (march_plane(W, H) && symmetric && opt.march) { launch_march_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM; }
-        return launch_blur_t<15, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+        return t.n == 15 ? launch_blur_n<15, NORM>(opt, st, in, out, W, H, t, mm, half, stop) : BLUR_NONE;
     } else {
-    if (march_plane(W, H) && symmetric && opt.march) {
-        switch (t.n) {
-            case 11: launch_march_t<11, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
-            case 15: launch_march_t<15, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
-            case 17: launch_march_t<17, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
-            case 21: launch_march_t<21, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
-            case 27: launch_march_t<27, NORM>(opt, st, in, out, W, H, t.t, mm, half, stop); return BLUR_TEAM;
-            default: break;
-        }
-    }
     switch (t.n) {
-        case 11: return launch_blur_t<11, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
-        case 15: return launch_blur_t<15, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
-        case 17: return launch_blur_t<17, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
-        case 21: return launch_blur_t<21, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
-        case 27: return launch_blur_t<27, NORM>(opt, st, in, out, W, H, t.t, symmetric, mm, half, stop);
+        case 11: return launch_blur_n<11, NORM>(opt, st, in, out, W, H, t, mm, half, stop);
+        case 15: return launch_blur_n<15, NORM>(opt, st, in, out, W, H, t, mm, half, stop);
+        case 17: return launch_blur_n<17, NORM>(opt, st, in, out, W, H, t, mm, half, stop);
+        case 21: return launch_blur_n<21, NORM>(opt, st, in, out, W, H, t, mm, half, stop);
+        case 27: return launch_blur_n<27, NORM>(opt, st, in, out, W, H, t, mm, half, stop);
         default: return BLUR_NONE;
     }
     }
@@ -503,10 +464,7 @@ bool launch_blur(siftmi_plan *p, const float *in, float *out, int W, int H, cons
 // kernel (init_sigma = 1.6); any other tap count goes through the convert pass.
 template <int DT>
 BlurForm launch_init_blur_dt(const Options &opt, hipStream_t st, const void *in, float *out, int W, int H, const Taps &t, const uint32_t *mm) {
-    if (t.n != 15) return BLUR_NONE;
-    const bool symmetric = taps_symmetric(t);
-    if (march_plane(W, H) && symmetric && opt.march) { launch_march_t<15, true, DT>(opt, st, in, out, W, H, t.t, mm); return BLUR_TEAM; }
-    return launch_blur_t<15, true, DT>(opt, st, in, out, W, H, t.t, symmetric, mm);
+    return t.n == 15 ? launch_blur_n<15, true, DT>(opt, st, in, out, W, H, t, mm) : BLUR_NONE;
 }
 
 // dispatch F(DT) over the typed-frame codes that have a fused path
@@ -542,6 +500,10 @@ struct Scope {   // optional hipEvent bracket around one launch (profile=1: blur
     ~Scope() { if (idx != (size_t)-1 && !stop_bound) hipEventRecord(p->events[idx].b, st); }
 };
 
+double tnow() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }   // host clock, us (option "host_timing")
+// the ordered words of the min / max slots (k_pyramid.hpp) back to floats
+float minmax_decode(uint32_t u) { uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; float f; memcpy(&f, &v, 4); return f; }
+
 int grid_for(int64_t n, int block, int max_blocks) {
     int64_t g = (n + block - 1) / block;
     if (g < 1) g = 1;
@@ -550,6 +512,104 @@ int grid_for(int64_t n, int block, int max_blocks) {
 }
 
 double contrast_threshold(const siftmi_params &par) { return 0.8 * (double)par.peak_thresh; }   // image.cl:152
+float octave_edge_thresh(const siftmi_params &par, int octsize) { return (octsize <= 1) ? par.edge_thresh0 : par.edge_thresh; }   // image.cl:193, plan.py:633-634
+
+// ---- one launch site per kernel ------------------------------------------------------------------------------------
+// Each function below is the only place that launches its kernel: it picks the template instance from a run-time argument
+// and holds the positional argument list once.  None knows a siftmi_plan: the plan's launch functions and the siftmi_stage_*
+// hooks both call them, and where the two differ (grid, capacities, cuts) the difference is an argument at the call site.
+// (The blur and gradient-map launches have the same shape: launch_blur_tiled, launch_init_blur_dt, launch_maps_kernel.)
+
+// Strip height and workgroup count of a detection launch over a W x H plane; blocks == 0: no detection area, no launch.
+// rows_opt > 0 fixes the strip height (option "ext_rows"), else extrema_strip_rows halves it until `min_strips` strips cover
+// the plane (<= 0: that function's own default).  y_lo >= 0: the band [y_lo, y_hi) is marched as a detection area of its
+// own.  Four strips (waves) per workgroup; behind the guard nx, ny >= 1, so there is at least one workgroup.
+struct DetectGeom { int rows = 0, blocks = 0; };
+DetectGeom detect_geometry(int W, int H, int border, int rows_opt, int min_strips, int y_lo, int y_hi) {
+    DetectGeom g;
+    if (!(W > 2 * border && H > 2 * border)) return g;
+    g.rows = rows_opt > 0 ? rows_opt : (min_strips > 0 ? extrema_strip_rows(W, H, border, min_strips) : extrema_strip_rows(W, H, border));
+    const int nx = (W - 2 * border + 61) / 62, ny = ((y_lo >= 0 ? y_hi - y_lo : H - 2 * border) + g.rows - 1) / g.rows;
+    g.blocks = (nx * ny + 3) / 4;
+    return g;
+}
+
+// extrema_kernel: `refine` picks the instance that also refines the survivors of the edge test (ra: where they go)
+void launch_extrema(hipStream_t st, bool refine, const DetectGeom &geo, const BlurPlanes &bp, int W, int H, int border, double contrast, float edth,
+                    float4 *cand, int *n_cand, int cand_cap, const RefineArgs &ra, int y_lo, int y_hi, int xcd_map) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)geo.blocks), dim3(256), 0, st, bp, W, H, border, geo.rows, contrast, edth, cand, n_cand, cand_cap, ra, y_lo, y_hi, xcd_map);
+    };
+    if (refine) go(extrema_kernel<true>); else go(extrema_kernel<false>);
+}
+
+// refine_kernel over the candidate list of one octave, `blocks` workgroups
+void launch_refine(hipStream_t st, int blocks, const BlurPlanes &bp, int W, int H, const float4 *cand, const int *n_cand, int cand_cap, const RefineArgs &ra) {
+    hipLaunchKernelGGL(refine_kernel, dim3((unsigned)blocks), dim3(256), 0, st, bp, W, H, cand, n_cand, cand_cap, ra.peak_thresh, ra.init_sigma, ra.kp, ra.kp_aux,
+                       ra.n_kp, ra.kp_capacity, ra.oct, ra.c_scale);
+}
+
+// orientation_kernel: `maps` picks the instance that reads tab.gmap / tab.omap; team_below: a workgroup per keypoint for groups
+// of fewer refined keypoints; small_blocks: the workgroups a group of fewer than 16384 keypoints uses
+void launch_orientation(hipStream_t st, bool maps, int grid, int lds_pad, const OctaveTable &tab, float ori_sigma, const float4 *kp, const int *kp_aux,
+                        Counters *cnt, int group, int kp_cap, float4 *okp, int *oaux, int out_cap, int team_below, int small_blocks) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), (size_t)lds_pad, st, tab, ori_sigma, kp, kp_aux, cnt, group, kp_cap, okp, oaux, out_cap, team_below, small_blocks);
+    };
+    if (maps) go(orientation_kernel<true>); else go(orientation_kernel<false>);
+}
+
+// The descriptor kernels: the row-interval forms (descriptor_kernel, lazy gradients or MAPS) or the streaming form (any window
+// size).  cnt == null: the keypoints [range_start, range_end), else the group's count.  The last four arguments are the
+// row-interval forms' alone: workgroup per keypoint below `team_below`, dynamic hand-out, the workgroups used by a group of
+// >= 65536 / < 16384 keypoints.
+enum DescForm { DESC_ROWS = 0, DESC_ROWS_MAPS = 1, DESC_STREAM = 2 };
+void launch_descriptors(hipStream_t st, DescForm form, int grid, int lds_pad, const OctaveTable &tab, const float4 *okp, const int *oaux, Counters *cnt, int group,
+                        int range_start, int range_end, int out_cap, KpRecord *records, int rec_cap, KpRecord *host_records, int host_cap,
+                        int team_below, int dynamic, int dense_blocks, int small_blocks) {
+    auto rows = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), (size_t)lds_pad, st, tab, okp, oaux, cnt, group, range_start, range_end, out_cap, records, rec_cap,
+                           host_records, host_cap, team_below, dynamic, dense_blocks, small_blocks);
+    };
+    if (form == DESC_ROWS_MAPS) rows(descriptor_kernel<true>);
+    else if (form == DESC_ROWS) rows(descriptor_kernel<false>);
+    else hipLaunchKernelGGL(descriptor_stream_kernel, dim3((unsigned)grid), dim3(256), (size_t)lds_pad, st, tab, okp, oaux, cnt, group, range_start, range_end, out_cap,
+                            records, rec_cap, host_records, host_cap);
+}
+
+// convert_kernel<T> / convert_rgb_kernel by frame format: n pixels of `src` -> f32.  false: `dt` has no convert kernel (f32 frames are not converted).
+bool launch_convert(hipStream_t st, int dt, const void *src, float *dst, int64_t n) {
+    const dim3 g(grid_for(n, 256, 4096));
+    switch (dt) {
+        case SIFTMI_U8: hipLaunchKernelGGL(convert_kernel<uint8_t>, g, dim3(256), 0, st, (const uint8_t *)src, dst, n); return true;
+        case SIFTMI_U16: hipLaunchKernelGGL(convert_kernel<uint16_t>, g, dim3(256), 0, st, (const uint16_t *)src, dst, n); return true;
+        case SIFTMI_U32: hipLaunchKernelGGL(convert_kernel<uint32_t>, g, dim3(256), 0, st, (const uint32_t *)src, dst, n); return true;
+        case SIFTMI_U64: hipLaunchKernelGGL(convert_kernel<uint64_t>, g, dim3(256), 0, st, (const uint64_t *)src, dst, n); return true;
+        case SIFTMI_I32: hipLaunchKernelGGL(convert_kernel<int32_t>, g, dim3(256), 0, st, (const int32_t *)src, dst, n); return true;
+        case SIFTMI_I64: hipLaunchKernelGGL(convert_kernel<int64_t>, g, dim3(256), 0, st, (const int64_t *)src, dst, n); return true;
+        case SIFTMI_F64: hipLaunchKernelGGL(convert_kernel<double>, g, dim3(256), 0, st, (const double *)src, dst, n); return true;
+        case SIFTMI_RGB8: hipLaunchKernelGGL(convert_rgb_kernel, g, dim3(256), 0, st, (const uint8_t *)src, dst, n); return true;
+        default: return false;
+    }
+}
+
+// normalize_kernel<DT>: n pixels of a frame of format `dt` (f32 or a typed format with a fused path) scaled by the min / max in mm
+void launch_normalize(hipStream_t st, int dt, const void *src, float *dst, int64_t n, const uint32_t *mm) {
+    const dim3 g(grid_for(n, 256, 4096));
+    if (dt == SIFTMI_F32) hipLaunchKernelGGL(normalize_kernel<0>, g, dim3(256), 0, st, src, dst, n, mm);
+    SIFTMI_TYPED_DISPATCH(dt, hipLaunchKernelGGL(normalize_kernel<DT>, g, dim3(256), 0, st, src, dst, n, mm));
+}
+
+// Global min / max of a frame of n pixels into mm: minmax_kernel for f32, minmax_typed_kernel<DT> for the typed formats with a fused
+// path (the callers pass no other).  At most `max_blocks` workgroups of `threads` threads (the typed kernel is built for 256).
+// reset / reset_words / reset_ones: the counter block this launch clears for the next image (k_pyramid.hpp: minmax_reset_next), or
+// null, 0, -1.  `stop` not null: bound to the launch (launch_ev).
+void launch_minmax(hipEvent_t stop, hipStream_t st, int dt, const void *img, int64_t n, int threads, int max_blocks, uint32_t *mm, uint32_t *reset,
+                   int reset_words, int reset_ones) {
+    if (dt == SIFTMI_F32) launch_ev(stop, minmax_kernel, dim3(grid_for(n / 4, threads, max_blocks)), dim3(threads), 0, st, (const float *)img, n, mm, reset, reset_words, reset_ones);
+    SIFTMI_TYPED_DISPATCH(dt, launch_ev(stop, minmax_typed_kernel<DT>, dim3(grid_for(n / TypedChunk<DT>::PX, threads, max_blocks)), dim3(threads), 0, st, img, n, mm,
+                                        reset, reset_words, reset_ones));
+}
 
 OctaveTable octave_table(const siftmi_plan *p) {
     OctaveTable tab;
@@ -653,7 +713,6 @@ int cand_group_of(const siftmi_plan *p, int oct) { return (oct == 1 && p->split_
 // of the octave's group (tagged with the octave).
 void launch_detect_octave(siftmi_plan *p, int oct, hipStream_t st) {
     const int W = p->ow[(size_t)oct], H = p->oh[(size_t)oct];
-    const int octsize = 1 << oct;
     const int g = group_of(p, oct);
     GroupLists &G = p->grp[g];
     p->groups_cur |= 1u << g;
@@ -664,36 +723,22 @@ void launch_detect_octave(siftmi_plan *p, int oct, hipStream_t st) {
     GroupLists &GC = p->grp[cand_group_of(p, oct)];
     const int ccap = (int)GC.cap_cand, kcap = (int)G.cap_kp;
     int *n_cand = &p->cnt->n_cand[oct];
-    if (!(W > 2 * border && H > 2 * border)) return;
-    const int rows = p->opt.ext_rows > 0 ? p->opt.ext_rows : extrema_strip_rows(W, H, border, p->opt.ext_strips);
-    const int nx = (W - 2 * border + 61) / 62, ny = (H - 2 * border + rows - 1) / rows;
-    const int blocks = std::max(1, (nx * ny + 3) / 4);
-    const float edth = (octsize <= 1) ? p->par.edge_thresh0 : p->par.edge_thresh;   // image.cl:193, plan.py:633-634
+    const DetectGeom geo = detect_geometry(W, H, border, p->opt.ext_rows, p->opt.ext_strips, -1, -1);
+    if (!geo.blocks) return;
     const RefineArgs ra = {p->par.peak_thresh, (float)p->par.init_sigma, G.kp, G.kp_aux, &p->cnt->g_kp[g], kcap, oct, &p->cnt->c_scale[oct][0]};
     // One launch detects and refines (the survivors of the edge test are refined by the wave that parked them: no
     // candidate list, no second launch) unless every stage is bracketed on its own (full profile) or option
     // "fused_refine" says otherwise (0: never, 1: planes below 1400^2, 2: every plane).
     const bool fused = p->profile <= 1 && (p->opt.fused_refine == 2 || (p->opt.fused_refine == 1 && !march_plane(W, H)));
-    if (fused) {
-        snprintf(lab, sizeof lab, "local_maxmin+interp_keypoint %d", oct);
-        Scope sc(p, lab, false, 0, st);
-        hipLaunchKernelGGL(extrema_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, bp, W, H, border, rows,
-                           contrast_threshold(p->par), edth, GC.cand, n_cand, ccap, ra, -1, -1, p->opt.xcd_map);
-        return;
-    }
     {
-        snprintf(lab, sizeof lab, "local_maxmin %d", oct);
+        snprintf(lab, sizeof lab, fused ? "local_maxmin+interp_keypoint %d" : "local_maxmin %d", oct);
         Scope sc(p, lab, false, 0, st);
-        hipLaunchKernelGGL(extrema_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, bp, W, H, border, rows,
-                           contrast_threshold(p->par), edth, GC.cand, n_cand, ccap, ra, -1, -1, p->opt.xcd_map);
+        launch_extrema(st, fused, geo, bp, W, H, border, contrast_threshold(p->par), octave_edge_thresh(p->par, 1 << oct), GC.cand, n_cand, ccap, ra, -1, -1, p->opt.xcd_map);
     }
-    {
-        snprintf(lab, sizeof lab, "interp_keypoint+compact %d", oct);
-        Scope sc(p, lab, false, 0, st);
-        hipLaunchKernelGGL(refine_kernel, dim3(512), dim3(256), 0, st, bp, W, H, (const float4 *)GC.cand,
-                           (const int *)n_cand, ccap, p->par.peak_thresh, (float)p->par.init_sigma, G.kp,
-                           G.kp_aux, &p->cnt->g_kp[g], kcap, oct, &p->cnt->c_scale[oct][0]);
-    }
+    if (fused) return;
+    snprintf(lab, sizeof lab, "interp_keypoint+compact %d", oct);
+    Scope sc(p, lab, false, 0, st);
+    launch_refine(st, 512, bp, W, H, GC.cand, n_cand, ccap, ra);
 }
 
 // First octave of the run that octave_tail_kernel takes (k_tail.hpp), or n_oct when it takes none: octaves >= 1 whose
@@ -728,7 +773,7 @@ int launch_tail(siftmi_plan *p, int first, hipStream_t st) {
         TailOctave &o = a.o[k];
         for (int s = 0; s < 6; s++) o.plane[s] = p->plane(oct, s);
         o.W = p->ow[(size_t)oct]; o.H = p->oh[(size_t)oct]; o.oct = oct;
-        o.edth = ((1 << oct) <= 1) ? p->par.edge_thresh0 : p->par.edge_thresh;   // image.cl:193, plan.py:633-634
+        o.edth = octave_edge_thresh(p->par, 1 << oct);
     }
     for (int s = 0; s < 5; s++) { a.taps[s] = p->taps[s].dev; a.ntaps[s] = p->taps[s].n; }
     const size_t lds = tail_lds_bytes(a.o[0].W, a.o[0].H);
@@ -760,16 +805,8 @@ void launch_orient_group(siftmi_plan *p, int group, hipStream_t st) {
     char lab[96];
     snprintf(lab, sizeof lab, "orientation_assignment group %d", group);
     Scope sc(p, lab, false, 0, st);
-    const int ori_blocks = p->opt.ori_blocks, ori_pad = p->opt.ori_pad;
-    const bool maps = group == 0 ? p->maps_g0 : p->maps_g1;
-    if (maps)
-        hipLaunchKernelGGL(orientation_kernel<true>, dim3((unsigned)ori_blocks), dim3(256), (size_t)ori_pad, st, tab, p->par.ori_sigma,
-                           (const float4 *)G.kp, (const int *)G.kp_aux, p->cnt, group, (int)G.cap_kp, G.okp, G.oaux, (int)G.cap_out,
-                           p->opt.ori_team, p->opt.ori_small_blocks);
-    else
-        hipLaunchKernelGGL(orientation_kernel<false>, dim3((unsigned)ori_blocks), dim3(256), (size_t)ori_pad, st, tab, p->par.ori_sigma,
-                           (const float4 *)G.kp, (const int *)G.kp_aux, p->cnt, group, (int)G.cap_kp, G.okp, G.oaux, (int)G.cap_out,
-                           p->opt.ori_team, p->opt.ori_small_blocks);
+    launch_orientation(st, group == 0 ? p->maps_g0 : p->maps_g1, p->opt.ori_blocks, p->opt.ori_pad, tab, p->par.ori_sigma, G.kp, G.kp_aux, p->cnt, group, (int)G.cap_kp,
+                       G.okp, G.oaux, (int)G.cap_out, p->opt.ori_team, p->opt.ori_small_blocks);
 }
 
 // descriptors of one group's oriented keypoints
@@ -789,26 +826,18 @@ void launch_descriptor_group(siftmi_plan *p, int group, hipStream_t st) {
     // headline -2.2 %, 4096^2 with every octave -2.5 %); on a 1024^2 frame that chain is short and the same cut costs 2 %
     const int small_blocks = (group == 0 && p->n_oct > 1 && march_plane(p->ow[0], p->oh[0])) ? (p->early_cur ? p->opt.desc_early_blocks : p->opt.desc_small_blocks) : desc_blocks;
     const int ocap = (int)G.cap_out, rcap = (int)std::min<int64_t>(p->cap_rec, 0x7fffffff);
-    if (p->desc_rows && !p->opt.desc_stream) {
-        // one launch, two forms: the count of the group (known on the device only) picks the wave-per-keypoint form
-        // (throughput) or the workgroup-per-keypoint form (latency of a sparse group)
-        const bool maps = group == 0 ? p->maps_g0 : p->maps_g1;
-        if (maps)
-            // (the MAPS form of a dense group wants every workgroup of the launch: 154 k keypoints 4.68 ms at 832, 4.48 at 960)
-            hipLaunchKernelGGL(descriptor_kernel<true>, dim3((unsigned)desc_blocks), dim3(256), (size_t)desc_pad, st, tab,
-                               (const float4 *)G.okp, (const int *)G.oaux, p->cnt, group, 0, 0, ocap, p->records, rcap, p->host_out, p->host_cap,
-                               p->opt.desc_team, p->opt.desc_dynamic, desc_blocks, small_blocks);
-        else
-            hipLaunchKernelGGL(descriptor_kernel<false>, dim3((unsigned)desc_blocks), dim3(256), (size_t)desc_pad, st, tab,
-                               (const float4 *)G.okp, (const int *)G.oaux, p->cnt, group, 0, 0, ocap, p->records, rcap, p->host_out, p->host_cap,
-                               p->opt.desc_team, p->opt.desc_dynamic, p->opt.desc_dense_blocks, small_blocks);
-    } else
-        hipLaunchKernelGGL(descriptor_stream_kernel, dim3((unsigned)desc_blocks), dim3(256), (size_t)desc_pad, st, tab,
-                           (const float4 *)G.okp, (const int *)G.oaux, p->cnt, group, 0, 0, ocap, p->records, rcap, p->host_out, p->host_cap);
+    // one launch, two forms: the count of the group (known on the device only) picks the wave-per-keypoint form
+    // (throughput) or the workgroup-per-keypoint form (latency of a sparse group) -- unless the windows need the streaming form
+    const bool maps = group == 0 ? p->maps_g0 : p->maps_g1;
+    const DescForm form = (p->desc_rows && !p->opt.desc_stream) ? (maps ? DESC_ROWS_MAPS : DESC_ROWS) : DESC_STREAM;
+    // (the MAPS form of a dense group wants every workgroup of the launch: 154 k keypoints 4.68 ms at 832, 4.48 at 960)
+    const int dense_blocks = maps ? desc_blocks : p->opt.desc_dense_blocks;
+    launch_descriptors(st, form, desc_blocks, desc_pad, tab, G.okp, G.oaux, p->cnt, group, 0, 0, ocap, p->records, rcap, p->host_out,
+                       p->host_cap, p->opt.desc_team, p->opt.desc_dynamic, dense_blocks, small_blocks);
 }
 
 // gradient_maps_kernel over the octaves [oct_lo, oct_hi) of `tab` into tab.gmap / tab.omap, at most `blocks` workgroups
-// walking the items with a grid stride (the plan's launch below and the stage hook siftmi_stage_gradient_maps)
+// walking the items with a grid stride (the plan's launch below and the stage hooks, on the null stream)
 void launch_maps_kernel(const OctaveTable &tab, int oct_lo, int oct_hi, int blocks, hipStream_t st) {
     long long total = 0;
     for (int o = oct_lo; o < oct_hi; o++) total += gradient_map_items_of(tab.W[o], tab.H[o]);
@@ -840,6 +869,7 @@ int launch_describe_group(siftmi_plan *p, int group, hipStream_t st, int slot) {
 }  // namespace
 
 // ============================================================================================
+thread_local std::string g_err;   // the calling thread's last error (declared in host_common.hpp)
 extern "C" {
 
 const char *siftmi_last_error(void) { return g_err.c_str(); }
@@ -1096,7 +1126,6 @@ int plan_enqueue(siftmi_plan *p, const void *image, int32_t image_dtype, int32_t
         p->raw_dtype = image_dtype;
     }
     const bool htime = p->opt.host_timing != 0;
-    auto tnow = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_enter = tnow();
     p->n_events = 0;
     if (p->profile > 1) hipEventRecord(p->ev_first, p->stream);     // (light profile: only the blur bracket -- every event record between kernels is a bubble)
@@ -1118,21 +1147,9 @@ int plan_enqueue(siftmi_plan *p, const void *image, int32_t image_dtype, int32_t
                           (!p->have_init || p->taps[5].n == 15) && p->opt.fused_convert;
     if (image_dtype != SIFTMI_F32 && !fused_in) {
         Scope sc(p, "convert -> float");
-        const int g = grid_for((int64_t)N, 256, 4096);
-        switch (image_dtype) {
-            case SIFTMI_U8: hipLaunchKernelGGL(convert_kernel<uint8_t>, dim3(g), dim3(256), 0, p->stream, (const uint8_t *)src, p->conv, (int64_t)N); break;
-            case SIFTMI_U16: hipLaunchKernelGGL(convert_kernel<uint16_t>, dim3(g), dim3(256), 0, p->stream, (const uint16_t *)src, p->conv, (int64_t)N); break;
-            case SIFTMI_U32: hipLaunchKernelGGL(convert_kernel<uint32_t>, dim3(g), dim3(256), 0, p->stream, (const uint32_t *)src, p->conv, (int64_t)N); break;
-            case SIFTMI_U64: hipLaunchKernelGGL(convert_kernel<uint64_t>, dim3(g), dim3(256), 0, p->stream, (const uint64_t *)src, p->conv, (int64_t)N); break;
-            case SIFTMI_I32: hipLaunchKernelGGL(convert_kernel<int32_t>, dim3(g), dim3(256), 0, p->stream, (const int32_t *)src, p->conv, (int64_t)N); break;
-            case SIFTMI_I64: hipLaunchKernelGGL(convert_kernel<int64_t>, dim3(g), dim3(256), 0, p->stream, (const int64_t *)src, p->conv, (int64_t)N); break;
-            case SIFTMI_F64: hipLaunchKernelGGL(convert_kernel<double>, dim3(g), dim3(256), 0, p->stream, (const double *)src, p->conv, (int64_t)N); break;
-            case SIFTMI_RGB8: hipLaunchKernelGGL(convert_rgb_kernel, dim3(g), dim3(256), 0, p->stream, (const uint8_t *)src, p->conv, (int64_t)N); break;
-            default: return fail(SIFTMI_EINVAL, "invalid input format");
-        }
+        if (!launch_convert(p->stream, image_dtype, src, p->conv, (int64_t)N)) return fail(SIFTMI_EINVAL, "invalid input format");
         f32src = p->conv;
     }
-    const int mm_blocks = p->opt.mm_blocks;
     // light profiling: ONE event pair around the six full-resolution blur launches (initial + five scales of octave 0),
     // opened by the END of the min/max launch and closed by the end of octave 0's last blur (enqueue_body) -- both events
     // ride on those launches (launch_ev), no packet of their own sits between two kernels
@@ -1144,14 +1161,9 @@ int plan_enqueue(siftmi_plan *p, const void *image, int32_t image_dtype, int32_t
     }
     {
         Scope sc(p, "max_min");
-        if (fused_in) {
-            SIFTMI_TYPED_DISPATCH(image_dtype, launch_ev(open_ev, minmax_typed_kernel<DT>, dim3(grid_for((int64_t)N / TypedChunk<DT>::PX, 256, mm_blocks)),
-                                                         dim3(256), 0, p->stream, src, (int64_t)N, p->mm, (uint32_t *)next_cnt, kCntWords, kCntOnes));
-        } else {
-            const int mm_threads = p->opt.mm_threads;
-            launch_ev(open_ev, minmax_kernel, dim3(grid_for((int64_t)N / 4, mm_threads, mm_blocks)), dim3(mm_threads), 0, p->stream, f32src,
-                      (int64_t)N, p->mm, (uint32_t *)next_cnt, kCntWords, kCntOnes);
-        }
+        // a typed frame is reduced where it lies (workgroups of 256), anything else as f32 (option "mm_threads")
+        launch_minmax(open_ev, p->stream, fused_in ? image_dtype : SIFTMI_F32, fused_in ? src : f32src, (int64_t)N, fused_in ? 256 : p->opt.mm_threads, p->opt.mm_blocks,
+                      p->mm, (uint32_t *)next_cnt, kCntWords, kCntOnes);
     }
     p->cnt_parity ^= 1;          // the pass that resets the other block is in the queue: the next image takes that block
     p->in_flight = true;
@@ -1167,18 +1179,10 @@ int plan_enqueue(siftmi_plan *p, const void *image, int32_t image_dtype, int32_t
         delete sc;
     } else {
         Scope sc(p, "normalize");
-        const dim3 g(grid_for((int64_t)N, 256, 4096));
-        if (fused_in) {
-            SIFTMI_TYPED_DISPATCH(image_dtype, hipLaunchKernelGGL(normalize_kernel<DT>, g, dim3(256), 0, p->stream, src, base0, (int64_t)N,
-                                                                   (const uint32_t *)p->mm));
-        } else {
-            hipLaunchKernelGGL(normalize_kernel<0>, g, dim3(256), 0, p->stream, (const void *)f32src, base0, (int64_t)N,
-                               (const uint32_t *)p->mm);
-        }
+        launch_normalize(p->stream, fused_in ? image_dtype : SIFTMI_F32, fused_in ? src : f32src, base0, (int64_t)N, p->mm);
     }
     // ---- everything below depends on plan-owned buffers only
-    int rc;
-    rc = enqueue_body(p);
+    const int rc = enqueue_body(p);
     if (htime) fprintf(stderr, "[siftmi] enqueue %.0f us\n", tnow() - t_enter);
     return rc;
 }
@@ -1450,10 +1454,7 @@ int plan_wait(siftmi_plan *p, int64_t *n_out, int32_t *overflow) {
     }
     if (!hcp) { drain_streams(p); return fail(SIFTMI_EDEVICE, "no complete copy of the image's counters came back"); }
     const Counters &hc = *hcp;
-    {
-        auto dec = [](uint32_t u) { uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; float f; memcpy(&f, &v, 4); return f; };
-        p->last_min = dec(hc.mm[0]); p->last_max = dec(hc.mm[1]);
-    }
+    p->last_min = minmax_decode(hc.mm[0]); p->last_max = minmax_decode(hc.mm[1]);
     if (!tail_timed_out && p->opt.tail_fault > 0 && p->opt.tail) { p->opt.tail_fault--; tail_timed_out = true; }   // injected (option "tail_fault")
     if (tail_timed_out) {
         // a workgroup of octave_tail_kernel stopped waiting for the octave above (k_tail.hpp): this image is incomplete.
@@ -1564,117 +1565,6 @@ int siftmi_plan_keypoints(siftmi_plan *p, const void *image, int32_t image_dtype
     return rc;
 }
 
-// ---- pinned host blocks for result arrays (size-bucketed pool: hipHostMalloc / hipHostFree cost 0.1-1 ms each)
-}  // extern "C"
-namespace {
-struct HostPool {
-    std::mutex mu;
-    std::unordered_map<void *, size_t> live;                 // block -> bucket size
-    std::unordered_map<size_t, std::vector<void *>> spare;   // bucket size -> free blocks
-    std::vector<void *> trash;                               // blocks to hand back to the driver at the next allocation
-    size_t live_bytes = 0, spare_bytes = 0;                  // handed out / parked in `spare`
-    size_t limit = (size_t)2 << 30;                          // page-locked bytes the pool may hold in all (siftmi_host_pool_limit)
-    static constexpr size_t kKeep = 8;                        // spare blocks kept per bucket
-};
-HostPool &host_pool() { static HostPool *hp = new HostPool(); return *hp; }   // leaked on purpose: no teardown order issues
-// Sizes round up to a power of two from 64 KiB to 1 MiB and to a multiple of 2 MiB above (a 3000 x 3000 float32 frame takes
-// 36 MiB, not 64: a stack-alignment loop keeps every aligned frame alive, and page-locked memory cannot be swapped).
-size_t host_bucket(size_t bytes) {
-    size_t bucket = (size_t)1 << 16;
-    while (bucket < bytes && bucket < ((size_t)1 << 20)) bucket <<= 1;
-    if (bucket < bytes) bucket = (bytes + (((size_t)2 << 20) - 1)) & ~(((size_t)2 << 20) - 1);
-    return bucket;
-}
-}  // namespace
-extern "C" {
-
-// The pool never holds more than `limit` bytes of page-locked memory (live + spare): beyond it siftmi_host_alloc returns
-// SIFTMI_ENOMEM and the Python layer hands out an ordinary array instead (one copy after the last kernel).
-int siftmi_host_pool_limit(int64_t limit_bytes, int64_t *live_bytes, int64_t *spare_bytes) {
-    HostPool &hp = host_pool();
-    std::lock_guard<std::mutex> g(hp.mu);
-    if (limit_bytes >= 0) hp.limit = (size_t)limit_bytes;
-    if (live_bytes) *live_bytes = (int64_t)hp.live_bytes;
-    if (spare_bytes) *spare_bytes = (int64_t)hp.spare_bytes;
-    return SIFTMI_OK;
-}
-
-int siftmi_host_alloc(int64_t bytes, void **out) {
-    if (!out || bytes < 0) return fail(SIFTMI_EINVAL, "bad argument");
-    *out = nullptr;
-    const size_t bucket = host_bucket((size_t)bytes);
-    HostPool &hp = host_pool();
-    std::vector<void *> drop;
-    {
-        std::lock_guard<std::mutex> g(hp.mu);
-        drop.swap(hp.trash);
-    }
-    for (void *q : drop) (void)hipHostFree(q);           // (what siftmi_host_free set aside: released here, in a caller's context)
-    drop.clear();
-    {
-        std::lock_guard<std::mutex> g(hp.mu);
-        auto it = hp.spare.find(bucket);
-        if (it != hp.spare.end() && !it->second.empty()) {
-            void *q = it->second.back();
-            it->second.pop_back();
-            hp.spare_bytes -= bucket;
-            hp.live[q] = bucket; hp.live_bytes += bucket;
-            *out = q;
-            return SIFTMI_OK;
-        }
-        if (hp.live_bytes + bucket > hp.limit)
-            return fail(SIFTMI_ENOMEM, "pinned result pool: %zu bytes live, %zu more would pass the limit of %zu (siftmi_host_pool_limit)",
-                        hp.live_bytes, bucket, hp.limit);
-        // room for the new block: spare blocks of other sizes go first
-        for (auto &kv : hp.spare) {
-            while (hp.live_bytes + hp.spare_bytes + bucket > hp.limit && !kv.second.empty()) {
-                drop.push_back(kv.second.back()); kv.second.pop_back(); hp.spare_bytes -= kv.first;
-            }
-        }
-    }
-    for (void *q : drop) (void)hipHostFree(q);
-    void *q = nullptr;
-    hipError_t e = hipHostMalloc(&q, bucket, hipHostMallocPortable | hipHostMallocMapped);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(SIFTMI_ENOMEM, "hipHostMalloc(%zu): %s", bucket, hipGetErrorString(e)); }
-    std::lock_guard<std::mutex> g(hp.mu);
-    hp.live[q] = bucket; hp.live_bytes += bucket;
-    *out = q;
-    return SIFTMI_OK;
-}
-
-// A block returns to the pool; nothing is handed back to the driver here (hipHostFree synchronises the device, and this runs
-// from a Python destructor): a block beyond what its bucket keeps (8 blocks, 3 from 16 MiB on) is set aside and released by
-// the next siftmi_host_alloc, or by siftmi_host_pool_trim.
-int siftmi_host_free(void *ptr) {
-    if (!ptr) return SIFTMI_OK;
-    HostPool &hp = host_pool();
-    std::lock_guard<std::mutex> g(hp.mu);
-    auto it = hp.live.find(ptr);
-    if (it == hp.live.end()) return fail(SIFTMI_EINVAL, "not a siftmi_host_alloc block");
-    const size_t bucket = it->second;
-    hp.live.erase(it);
-    hp.live_bytes -= bucket;
-    std::vector<void *> &v = hp.spare[bucket];
-    if (v.size() < (bucket >= ((size_t)16 << 20) ? (size_t)3 : HostPool::kKeep)) { v.push_back(ptr); hp.spare_bytes += bucket; }
-    else hp.trash.push_back(ptr);
-    return SIFTMI_OK;
-}
-
-// Release spare blocks until at most `keep_bytes` of them remain (0: all).  Synchronises the device (hipHostFree).
-int siftmi_host_pool_trim(int64_t keep_bytes) {
-    HostPool &hp = host_pool();
-    std::vector<void *> drop;
-    {
-        std::lock_guard<std::mutex> g(hp.mu);
-        drop.swap(hp.trash);
-        for (auto &kv : hp.spare)
-            while ((int64_t)hp.spare_bytes > keep_bytes && !kv.second.empty()) {
-                drop.push_back(kv.second.back()); kv.second.pop_back(); hp.spare_bytes -= kv.first;
-            }
-    }
-    for (void *q : drop) (void)hipHostFree(q);
-    return SIFTMI_OK;
-}
 
 int siftmi_plan_fetch(siftmi_plan *p, siftmi_keypoint *out, int32_t out_is_device, int64_t first, int64_t count) {
     if (!p || (count > 0 && !out)) return fail(SIFTMI_EINVAL, "null argument");
@@ -1916,7 +1806,6 @@ int siftmi_batch_keypoints_into(siftmi_batch *b, const void *const *images, int3
 #define BATCHCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess && !rc) rc = fail(e_ == hipErrorOutOfMemory ? SIFTMI_ENOMEM : SIFTMI_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
     if (images_are_device) BATCHCHK(hipDeviceSynchronize());   // once per batch: order after the caller's streams
     const bool htime = L > 0 && b->lanes[0]->opt.host_timing;   // diagnostic: where the host thread spends the batch
-    auto tnow = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_retire = 0, t_enqueue = 0;
     // host frames go through the upload ring (see siftmi_batch)
     const bool staged = !images_are_device && n_images > 0 && L > 0;
@@ -2133,352 +2022,6 @@ int siftmi_plan_blur_ms(const siftmi_plan *p, int32_t octave, float *blur_ms, in
     return SIFTMI_OK;
 }
 
-// ============================================================================================
-// MatchPlan
-}  // extern "C"
-
-struct siftmi_matcher {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int64_t size = 0;
-    int profile = 0;
-    uint8_t *kp1 = nullptr, *kp2 = nullptr;
-    int64_t cap1 = 0, cap2 = 0;
-    int2 *pairs = nullptr;
-    int64_t cap_pairs = 0;
-    MatchPartial *partial = nullptr;
-    int64_t cap_partial = 0;
-    int *counter = nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    float last_ms = 0;
-    // profile != 0: the events of match.py:226-263 -- "copy H->D KP_1", "copy H->D KP_2", "matching", "copy D->H match" -- as
-    // device times of the last call in ms (-1: the stage did not run: a device-resident list, no pair to copy)
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    float stage_ms[4] = {-1.f, -1.f, -1.f, -1.f};
-    // ROI mask (MatchPlan.set_roi, match.py:312-320) and the scratch of the masked / mutual variants
-    int8_t *roi = nullptr;
-    int64_t cap_roi = 0;
-    int roi_w = 0, roi_h = 0;
-    uint8_t *q1 = nullptr, *l1 = nullptr, *q2 = nullptr, *l2 = nullptr;   // per-keypoint flags (as query / as list element)
-    int64_t cap_q1 = 0, cap_l1 = 0, cap_q2 = 0, cap_l2 = 0;
-    int *nearest = nullptr;
-    int64_t cap_nearest = 0;
-    int2 *pairs2 = nullptr;
-    int64_t cap_pairs2 = 0;
-    // consensus filter (siftmi_match_consensus): the gathered matches, the hypotheses and their votes; grown on demand
-    float4 *c_pts = nullptr;
-    uint8_t *c_mask = nullptr, *c_valid = nullptr;
-    float *c_models = nullptr;
-    int *c_votes = nullptr;
-    int64_t cap_c_pts = 0, cap_c_mask = 0, cap_c_valid = 0, cap_c_models = 0, cap_c_votes = 0;
-    ConsensusResult *c_result = nullptr;
-    hipEvent_t ec_a = nullptr, ec_b = nullptr;
-};
-
-namespace {
-int ensure(void **ptr, int64_t *cap, int64_t need, size_t elem) {
-    if (need <= *cap && *ptr) return SIFTMI_OK;
-    if (*ptr) hipFree(*ptr);
-    *ptr = nullptr; *cap = 0;
-    hipError_t e = hipMalloc(ptr, (size_t)(need > 0 ? need : 1) * elem);
-    if (e != hipSuccess) return fail(SIFTMI_ENOMEM, "hipMalloc(%lld x %zu): %s", (long long)need, elem, hipGetErrorString(e));
-    *cap = need;
-    return SIFTMI_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int siftmi_match_create(int64_t size, int32_t device_id, int32_t profile, siftmi_matcher **out) {
-    if (!out) return fail(SIFTMI_EINVAL, "null argument");
-    *out = nullptr;
-    if (size < 1) return fail(SIFTMI_EINVAL, "size must be >= 1");
-    int ndev = siftmi_device_count();
-    if (ndev < 1) return fail(SIFTMI_EDEVICE, "no HIP device available");
-    if (device_id < 0 || device_id >= ndev) return fail(SIFTMI_EINVAL, "device %d out of range", device_id);
-    HIPCHK(hipSetDevice(device_id));
-    siftmi_matcher *m = new (std::nothrow) siftmi_matcher();
-    if (!m) return fail(SIFTMI_ENOMEM, "host allocation failed");
-    m->device = device_id; m->size = size; m->profile = profile;
-    int rc = SIFTMI_OK;
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(SIFTMI_EDEVICE, "hipStreamCreate failed");
-    if (!rc) rc = ensure((void **)&m->kp1, &m->cap1, size, 144);
-    if (!rc) rc = ensure((void **)&m->kp2, &m->cap2, size, 144);
-    if (!rc) rc = ensure((void **)&m->pairs, &m->cap_pairs, size, sizeof(int2));
-    if (!rc && hipMalloc((void **)&m->counter, 16) != hipSuccess) rc = fail(SIFTMI_ENOMEM, "hipMalloc failed");
-    if (!rc) { hipEventCreate(&m->ea); hipEventCreate(&m->eb); hipEventCreate(&m->ec_a); hipEventCreate(&m->ec_b); }
-    if (!rc && profile) for (hipEvent_t &e : m->ev) if (hipEventCreate(&e) != hipSuccess) rc = fail(SIFTMI_EDEVICE, "hipEventCreate failed");
-    if (rc) { std::string keep = g_err; siftmi_match_destroy(m); g_err = keep; return rc; }
-    *out = m;
-    return SIFTMI_OK;
-}
-
-int siftmi_match_destroy(siftmi_matcher *m) {
-    if (!m) return SIFTMI_OK;
-    hipSetDevice(m->device);
-    if (m->stream) hipStreamSynchronize(m->stream);
-    if (m->kp1) hipFree(m->kp1);
-    if (m->kp2) hipFree(m->kp2);
-    if (m->pairs) hipFree(m->pairs);
-    if (m->partial) hipFree(m->partial);
-    for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
-                    (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result})
-        if (q) hipFree(q);
-    if (m->ec_a) hipEventDestroy(m->ec_a);
-    if (m->ec_b) hipEventDestroy(m->ec_b);
-    if (m->counter) hipFree(m->counter);
-    if (m->ea) hipEventDestroy(m->ea);
-    if (m->eb) hipEventDestroy(m->eb);
-    for (hipEvent_t e : m->ev) if (e) hipEventDestroy(e);
-    if (m->stream) hipStreamDestroy(m->stream);
-    delete m;
-    return SIFTMI_OK;
-}
-
-int siftmi_match_set_roi(siftmi_matcher *m, const int8_t *roi, int32_t roi_width, int32_t roi_height) {
-    if (!m) return fail(SIFTMI_EINVAL, "null matcher");
-    HIPCHK(hipSetDevice(m->device));
-    if (!roi) { m->roi_w = m->roi_h = 0; return SIFTMI_OK; }       // unset_roi
-    if (roi_width < 1 || roi_height < 1) return fail(SIFTMI_EINVAL, "bad ROI shape %d x %d", roi_width, roi_height);
-    int rc = ensure((void **)&m->roi, &m->cap_roi, (int64_t)roi_width * roi_height, 1);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(m->roi, roi, (size_t)roi_width * roi_height, hipMemcpyHostToDevice));
-    m->roi_w = roi_width; m->roi_h = roi_height;
-    return SIFTMI_OK;
-}
-
-namespace {
-// one direction of the brute-force scan: partials of `nq` queries against `nl` list elements, folded by the merge kernel
-int match_direction(siftmi_matcher *m, const uint8_t *dq, int64_t nq, const uint8_t *dl, int64_t nl, const uint8_t *qflag,
-                    const uint8_t *lflag, float ratio_th, int2 *pairs, int cap, int *nearest) {
-    // 2-D decomposition: query blocks x partitions of the list, enough workgroups to fill 256 CUs
-    const int qblocks = (int)((nq + 256 * SIFT_MATCH_QPT - 1) / (256 * SIFT_MATCH_QPT));
-    int nparts = (2048 + qblocks - 1) / qblocks;
-    const int max_parts = (int)((nl + 4 * SIFT_MATCH_TILE - 1) / (4 * SIFT_MATCH_TILE));
-    if (nparts > max_parts) nparts = max_parts;
-    const int min_parts = (int)((nl + SIFT_MATCH_MAX_PART - 1) / SIFT_MATCH_MAX_PART);     // 16-bit index inside a partition
-    if (nparts < min_parts) nparts = min_parts;
-    if (nparts < 1) nparts = 1;
-    int part_len = (int)((nl + nparts - 1) / nparts);
-    part_len = (part_len + SIFT_MATCH_TILE - 1) / SIFT_MATCH_TILE * SIFT_MATCH_TILE;
-    nparts = (int)((nl + part_len - 1) / part_len);
-    int rc;
-    if ((rc = ensure((void **)&m->partial, &m->cap_partial, (int64_t)nparts * nq, sizeof(MatchPartial)))) return rc;
-    const dim3 grid((unsigned)qblocks, (unsigned)nparts);
-    if (lflag)
-        hipLaunchKernelGGL(match_partial_kernel<true>, grid, dim3(256), 0, m->stream, dq, (int)nq, dl, (int)nl, part_len, m->partial, qflag, lflag);
-    else
-        hipLaunchKernelGGL(match_partial_kernel<false>, grid, dim3(256), 0, m->stream, dq, (int)nq, dl, (int)nl, part_len, m->partial,
-                           (const uint8_t *)nullptr, (const uint8_t *)nullptr);
-    hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, m->stream,
-                       (const MatchPartial *)m->partial, (int)nq, nparts, ratio_th, pairs, m->counter, cap, qflag, nearest);
-    return SIFTMI_OK;
-}
-}  // namespace
-
-int siftmi_match_ex(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
-                    const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t roi_mode,
-                    int32_t mutual, int32_t *pairs, int64_t capacity, int64_t *n_out, int64_t *n_total) {
-    if (!m || !n_out) return fail(SIFTMI_EINVAL, "null argument");
-    if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
-    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
-    if (roi_mode < 0 || roi_mode > 2) return fail(SIFTMI_EINVAL, "roi_mode must be 0 (off), 1 (matching_valid) or 2 (strict)");
-    if (roi_mode && !(m->roi && m->roi_w > 0)) return fail(SIFTMI_EINVAL, "roi_mode %d without a region of interest (siftmi_match_set_roi)", roi_mode);
-    HIPCHK(hipSetDevice(m->device));
-    *n_out = 0;
-    if (n_total) *n_total = 0;
-    for (float &v : m->stage_ms) v = -1.f;
-    if (n1 == 0 || n2 == 0) return SIFTMI_OK;   // dist1 == dist2 == 1e12 -> ratio 1, never < ratio_th
-    if (kp1_is_device || kp2_is_device) HIPCHK(hipDeviceSynchronize());
-    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
-    int rc;
-    const bool prof = m->profile && m->ev[0];
-    if (prof) hipEventRecord(m->ev[0], m->stream);
-    if (!kp1_is_device) {
-        if ((rc = ensure((void **)&m->kp1, &m->cap1, n1, 144))) return rc;
-        HIPCHK(hipMemcpyAsync(m->kp1, kp1, (size_t)n1 * 144, hipMemcpyHostToDevice, m->stream));
-        d1 = m->kp1;
-    }
-    if (prof) hipEventRecord(m->ev[1], m->stream);
-    if (!kp2_is_device) {
-        if ((rc = ensure((void **)&m->kp2, &m->cap2, n2, 144))) return rc;
-        HIPCHK(hipMemcpyAsync(m->kp2, kp2, (size_t)n2 * 144, hipMemcpyHostToDevice, m->stream));
-        d2 = m->kp2;
-    }
-    if (prof) hipEventRecord(m->ev[2], m->stream);
-    // match.py:241-243,252: output capacity = max(self.kpsize, min(n1, n2))
-    int64_t cap = m->size;
-    if ((n1 < n2 ? n1 : n2) > cap) cap = (n1 < n2 ? n1 : n2);
-    if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, cap, sizeof(int2)))) return rc;
-    HIPCHK(hipMemsetAsync(m->counter, 0, 8, m->stream));
-    hipEventRecord(m->ea, m->stream);
-    const uint8_t *qf1 = nullptr, *lf2 = nullptr;
-    if (roi_mode) {
-        if ((rc = ensure((void **)&m->q1, &m->cap_q1, n1, 1)) || (rc = ensure((void **)&m->l1, &m->cap_l1, n1, 1)) ||
-            (rc = ensure((void **)&m->q2, &m->cap_q2, n2, 1)) || (rc = ensure((void **)&m->l2, &m->cap_l2, n2, 1))) return rc;
-        hipLaunchKernelGGL(match_roi_flags_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, d1, (int)n1,
-                           (const int8_t *)m->roi, m->roi_w, m->roi_h, roi_mode, m->q1, m->l1);
-        hipLaunchKernelGGL(match_roi_flags_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, m->stream, d2, (int)n2,
-                           (const int8_t *)m->roi, m->roi_w, m->roi_h, roi_mode, m->q2, m->l2);
-        qf1 = m->q1; lf2 = m->l2;
-    }
-    if ((rc = match_direction(m, d1, n1, d2, n2, qf1, lf2, ratio_th, m->pairs, (int)cap, nullptr))) return rc;
-    int2 *result = m->pairs;
-    int *result_counter = m->counter;
-    int count = 0;
-    if (mutual) {
-        // reverse scan: nearest list-1 keypoint of every list-2 keypoint over the same masked distances
-        if ((rc = ensure((void **)&m->nearest, &m->cap_nearest, n2, sizeof(int))) ||
-            (rc = ensure((void **)&m->pairs2, &m->cap_pairs2, cap, sizeof(int2)))) return rc;
-        const uint8_t *qf2 = nullptr, *lf1 = nullptr;
-        if (roi_mode) {
-            hipLaunchKernelGGL(match_reverse_flags_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, m->stream, (const uint8_t *)m->l2, (int)n2, m->q2);
-            hipLaunchKernelGGL(match_reverse_list_flags_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, (const uint8_t *)m->q1, (int)n1, m->l1);
-            qf2 = m->q2; lf1 = m->l1;
-        }
-        HIPCHK(hipMemcpyAsync(&count, m->counter, 4, hipMemcpyDeviceToHost, m->stream));   // forward count (the partial buffer is reused below)
-        if ((rc = match_direction(m, d2, n2, d1, n1, qf2, lf1, ratio_th, nullptr, 0, m->nearest))) return rc;
-        HIPCHK(hipStreamSynchronize(m->stream));
-        const int nfwd = count < cap ? count : (int)cap;
-        if (nfwd > 0)
-            hipLaunchKernelGGL(match_mutual_filter_kernel, dim3((unsigned)((nfwd + 255) / 256)), dim3(256), 0, m->stream,
-                               (const int2 *)m->pairs, nfwd, (const int *)m->nearest, m->pairs2, m->counter + 1);
-        result = m->pairs2; result_counter = m->counter + 1;
-    }
-    hipEventRecord(m->eb, m->stream);
-    HIPCHK(hipMemcpyAsync(&count, result_counter, 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipGetLastError());
-    hipEventElapsedTime(&m->last_ms, m->ea, m->eb);
-    if (n_total) *n_total = count;
-    int64_t n = count < cap ? count : cap;
-    rc = SIFTMI_OK;
-    if (n > capacity) { n = capacity; rc = SIFTMI_ECAPACITY; g_err = "pair capacity too small; result truncated"; }
-    if (prof) {
-        m->stage_ms[2] = m->last_ms;
-        if (!kp1_is_device) hipEventElapsedTime(&m->stage_ms[0], m->ev[0], m->ev[1]);
-        if (!kp2_is_device) hipEventElapsedTime(&m->stage_ms[1], m->ev[1], m->ev[2]);
-    }
-    if (n > 0) {
-        if (!pairs) return fail(SIFTMI_EINVAL, "null pairs buffer");
-        if (prof) {
-            hipEventRecord(m->ev[3], m->stream);
-            HIPCHK(hipMemcpyAsync(pairs, result, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost, m->stream));
-            hipEventRecord(m->ev[4], m->stream);
-            HIPCHK(hipStreamSynchronize(m->stream));
-            hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
-        } else {
-            HIPCHK(hipMemcpy(pairs, result, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
-        }
-    }
-    *n_out = n;
-    return rc;
-}
-
-int siftmi_match(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
-                 const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t *pairs,
-                 int64_t capacity, int64_t *n_out, int64_t *n_total) {
-    return siftmi_match_ex(m, kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, ratio_th, 0, 0, pairs, capacity, n_out, n_total);
-}
-
-// Consensus filter over the pairs of a match (k_consensus.hpp; the contract is DESIGN.md section 7 row 5).  The lists and the
-// pairs are used where they lie; host ones are staged in the matcher's own buffers.
-int siftmi_match_consensus(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
-                           const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
-                           const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
-                           int32_t n_hyp, float tol, uint32_t seed, uint8_t *mask, float *model, int32_t *winner,
-                           int32_t *winner_votes, int32_t *votes_all, float *models_all, double *kernel_ms) {
-    if (!m || !winner) return fail(SIFTMI_EINVAL, "null argument");
-    if (n1 < 0 || n2 < 0 || n_pairs < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff || n_pairs > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
-    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
-    if (n_pairs > 0 && (!pairs || !mask)) return fail(SIFTMI_EINVAL, "null pairs or mask with %lld pairs", (long long)n_pairs);
-    if (n_hyp < 1 || n_hyp > (1 << 20)) return fail(SIFTMI_EINVAL, "n_hyp %d outside 1..2^20", n_hyp);
-    if (!std::isfinite(tol) || !(tol > 0.f)) return fail(SIFTMI_EINVAL, "tol must be finite and > 0");
-    HIPCHK(hipSetDevice(m->device));
-    *winner = -1;
-    if (winner_votes) *winner_votes = 0;
-    if (kernel_ms) *kernel_ms = 0.0;
-    if (n_pairs < 3) {      // every triple repeats an index: nothing can win, nothing is launched
-        if (n_pairs > 0) memset(mask, 0, (size_t)n_pairs);
-        if (votes_all) memset(votes_all, 0, sizeof(int32_t) * (size_t)n_hyp);
-        if (models_all) for (int64_t i = 0; i < (int64_t)n_hyp * 6; i++) models_all[i] = std::nanf("");
-        return SIFTMI_OK;
-    }
-    if (kp1_is_device || kp2_is_device || pairs_is_device) HIPCHK(hipDeviceSynchronize());
-    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
-    const int2 *dp = (const int2 *)pairs;
-    int rc;
-    if (!kp1_is_device && n1 > 0) {
-        if ((rc = ensure((void **)&m->kp1, &m->cap1, n1, 144))) return rc;
-        HIPCHK(hipMemcpyAsync(m->kp1, kp1, (size_t)n1 * 144, hipMemcpyHostToDevice, m->stream));
-        d1 = m->kp1;
-    }
-    if (!kp2_is_device && n2 > 0) {
-        if ((rc = ensure((void **)&m->kp2, &m->cap2, n2, 144))) return rc;
-        HIPCHK(hipMemcpyAsync(m->kp2, kp2, (size_t)n2 * 144, hipMemcpyHostToDevice, m->stream));
-        d2 = m->kp2;
-    }
-    if (!pairs_is_device) {
-        if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, n_pairs, sizeof(int2)))) return rc;
-        HIPCHK(hipMemcpyAsync(m->pairs, pairs, (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, m->stream));
-        dp = m->pairs;
-    }
-    if ((rc = ensure((void **)&m->c_pts, &m->cap_c_pts, n_pairs, sizeof(float4))) ||
-        (rc = ensure((void **)&m->c_mask, &m->cap_c_mask, n_pairs, 1)) ||
-        (rc = ensure((void **)&m->c_valid, &m->cap_c_valid, n_hyp, 1)) ||
-        (rc = ensure((void **)&m->c_models, &m->cap_c_models, (int64_t)n_hyp * 6, sizeof(float))) ||
-        (rc = ensure((void **)&m->c_votes, &m->cap_c_votes, n_hyp, sizeof(int)))) return rc;
-    if (!m->c_result) HIPCHK(hipMalloc((void **)&m->c_result, sizeof(ConsensusResult)));
-    const int M = (int)n_pairs, H = n_hyp;
-    const float tol2 = tol * tol;
-    const unsigned mblocks = (unsigned)((M + 255) / 256);
-    hipLaunchKernelGGL(consensus_gather_kernel, dim3(mblocks), dim3(256), 0, m->stream, d1, (int)n1, d2, (int)n2, dp, M, m->c_pts);
-    hipLaunchKernelGGL(consensus_solve_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, m->stream, (const float4 *)m->c_pts,
-                       (uint32_t)M, H, seed, m->c_models, m->c_valid, m->c_votes);
-    // vote grid: tiles of matches x chunks of hypotheses, about eight workgroups per CU; a chunk is at most the kernel's LDS counters
-    // and at least 16 hypotheses (a workgroup's loads of its matches must be worth its walk)
-    const int tiles = (M + SIFT_CONS_TILE - 1) / SIFT_CONS_TILE;
-    int chunks = (2048 + tiles - 1) / tiles;
-    const int min_chunks = (H + SIFT_CONS_HMAX - 1) / SIFT_CONS_HMAX, max_chunks = (H + 15) / 16;
-    if (chunks > max_chunks) chunks = max_chunks;
-    if (chunks < min_chunks) chunks = min_chunks;
-    const int h_chunk = (H + chunks - 1) / chunks;
-    chunks = (H + h_chunk - 1) / h_chunk;
-    hipEventRecord(m->ec_a, m->stream);
-    hipLaunchKernelGGL(consensus_vote_kernel, dim3((unsigned)tiles, (unsigned)chunks), dim3(SIFT_CONS_THREADS), 0, m->stream,
-                       (const float4 *)m->c_pts, M, (const float *)m->c_models, H, h_chunk, tol2, m->c_votes);
-    hipEventRecord(m->ec_b, m->stream);
-    hipLaunchKernelGGL(consensus_select_kernel, dim3(1), dim3(256), 0, m->stream, (const int *)m->c_votes, (const uint8_t *)m->c_valid,
-                       (const float *)m->c_models, H, m->c_result);
-    hipLaunchKernelGGL(consensus_mask_kernel, dim3(mblocks), dim3(256), 0, m->stream, (const float4 *)m->c_pts, M,
-                       (const ConsensusResult *)m->c_result, tol2, m->c_mask);
-    ConsensusResult res;
-    HIPCHK(hipMemcpyAsync(&res, m->c_result, sizeof res, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(mask, m->c_mask, (size_t)M, hipMemcpyDeviceToHost, m->stream));
-    if (votes_all) HIPCHK(hipMemcpyAsync(votes_all, m->c_votes, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, m->stream));
-    if (models_all) HIPCHK(hipMemcpyAsync(models_all, m->c_models, sizeof(float) * 6 * (size_t)H, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipGetLastError());
-    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
-    *winner = res.winner;
-    if (winner_votes) *winner_votes = res.votes;
-    if (res.winner >= 0 && model) memcpy(model, res.model, sizeof res.model);
-    return SIFTMI_OK;
-}
-
-int siftmi_match_last_kernel_ms(const siftmi_matcher *m, float *ms) {
-    if (!m || !ms) return fail(SIFTMI_EINVAL, "null argument");
-    *ms = m->last_ms;
-    return SIFTMI_OK;
-}
-
-int siftmi_match_last_stage_ms(const siftmi_matcher *m, float *ms4) {
-    if (!m || !ms4) return fail(SIFTMI_EINVAL, "null argument");
-    if (!m->profile) return fail(SIFTMI_EINVAL, "the matcher was created without profiling");
-    for (int i = 0; i < 4; i++) ms4[i] = m->stage_ms[i];
-    return SIFTMI_OK;
-}
-
 }  // extern "C"
 
 // ============================================================================================
@@ -2515,17 +2058,41 @@ int stage_end() {
     return SIFTMI_OK;
 }
 
-// the plan's map launch on the null stream; blocks: width of the grid stride (0: the plan's default)
-void stage_maps_launch(const OctaveTable &tab, int oct_lo, int oct_hi, int blocks) {
-    launch_maps_kernel(tab, oct_lo, oct_hi, blocks > 0 ? blocks : g_default_options.maps_blocks, 0);
-}
-
 // octave of a power-of-two octsize
 int stage_octave(int32_t octsize, int &oct) {
     oct = 0;
     while ((1 << oct) < octsize && oct < SIFT_MAX_OCTAVES - 1) oct++;
     return (1 << oct) == octsize ? SIFTMI_OK : fail(SIFTMI_EINVAL, "octsize must be a power of two");
 }
+
+// host taps -> Taps with its device copy (kept alive by `store`)
+int stage_taps(const float *taps, int ntaps, DevBuf &store, Taps &tp) {
+    tp.n = ntaps;
+    for (int i = 0; i < ntaps; i++) tp.t[i] = taps[i];
+    int rc = store.upload(tp.t, sizeof tp.t);
+    if (rc) return rc;
+    tp.dev = store.as<float>();
+    return SIFTMI_OK;
+}
+
+// What the per-keypoint hooks put on the device: the six planes of ONE octave and the table that holds nothing else, the
+// keypoints with their aux tags (detection scale | octave << 8) and, for the MAPS forms, room for the octave's gradient maps.
+struct StageOctave {
+    DevBuf b, k, ks, gm, om;
+    OctaveTable tab;
+    int upload(const float *blurs, int W, int H, int oct, const float *kps, const int32_t *kp_scale, int64_t n, bool maps) {
+        const size_t N = (size_t)W * H;
+        std::vector<int32_t> aux((size_t)n);
+        for (int64_t i = 0; i < n; i++) aux[(size_t)i] = kp_scale[i] | (oct << 8);
+        int rc;
+        if ((rc = b.upload(blurs, 6 * N * 4)) || (rc = k.upload(kps, (size_t)n * 16)) || (rc = ks.upload(aux.data(), (size_t)n * 4))) return rc;
+        if (maps && ((rc = gm.alloc(3 * N * 4)) || (rc = om.alloc(3 * N * 4)))) return rc;
+        memset(&tab, 0, sizeof tab);
+        tab.base = b.as<float>(); tab.off[oct] = 0; tab.W[oct] = W; tab.H[oct] = H;
+        tab.gmap = gm.as<float>(); tab.omap = om.as<float>();
+        return SIFTMI_OK;
+    }
+};
 
 // the MAPS forms read the maps of detection scales 1..3 only
 int stage_maps_scales(const int32_t *kp_scale, int64_t n) {
@@ -2560,14 +2127,13 @@ int siftmi_stage_minmax_normalize(int32_t dev, const float *in, float *out, int3
     DevBuf a, b, mm;
     if ((rc = a.upload(in, N * 4)) || (rc = b.alloc(N * 4)) || (rc = mm.alloc(8))) return rc;
     hipLaunchKernelGGL(minmax_init, dim3(1), dim3(1), 0, 0, mm.as<uint32_t>());
-    hipLaunchKernelGGL(minmax_kernel, dim3(grid_for((int64_t)N / 4, 256, 2048)), dim3(256), 0, 0, a.as<float>(), (int64_t)N, mm.as<uint32_t>());
-    hipLaunchKernelGGL(normalize_kernel<0>, dim3(grid_for((int64_t)N, 256, 4096)), dim3(256), 0, 0, (const void *)a.as<float>(), b.as<float>(), (int64_t)N, (const uint32_t *)mm.as<uint32_t>());
+    launch_minmax(nullptr, 0, SIFTMI_F32, a.p, (int64_t)N, 256, 2048, mm.as<uint32_t>(), nullptr, 0, -1);     // (no counter block to reset)
+    launch_normalize(0, SIFTMI_F32, a.p, b.as<float>(), (int64_t)N, mm.as<uint32_t>());
     if ((rc = stage_end())) return rc;
     uint32_t h[2];
     HIPCHK(hipMemcpy(h, mm.p, 8, hipMemcpyDeviceToHost));
-    auto dec = [](uint32_t u) { uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; float f; memcpy(&f, &v, 4); return f; };
-    if (mn) *mn = dec(h[0]);
-    if (mx) *mx = dec(h[1]);
+    if (mn) *mn = minmax_decode(h[0]);
+    if (mx) *mx = minmax_decode(h[1]);
     if (out) HIPCHK(hipMemcpy(out, b.p, N * 4, hipMemcpyDeviceToHost));
     return SIFTMI_OK;
 }
@@ -2578,10 +2144,8 @@ int siftmi_stage_blur(int32_t dev, const float *in, float *out, int32_t W, int32
     const size_t N = (size_t)W * H;
     DevBuf a, b, t, dt;
     if ((rc = a.upload(in, N * 4)) || (rc = b.alloc(N * 4)) || (rc = t.alloc(N * 4))) return rc;
-    Taps tp; tp.n = ntaps;
-    for (int i = 0; i < ntaps; i++) tp.t[i] = taps[i];
-    if ((rc = dt.upload(tp.t, sizeof tp.t))) return rc;
-    tp.dev = dt.as<float>();
+    Taps tp;
+    if ((rc = stage_taps(taps, ntaps, dt, tp))) return rc;
     if (!launch_blur_tiled<false>(g_default_options, 0, a.as<float>(), b.as<float>(), W, H, tp, nullptr))
         launch_blur_generic(0, a.as<float>(), b.as<float>(), t.as<float>(), W, H, tp, nullptr, false);
     if ((rc = stage_end())) return rc;
@@ -2603,10 +2167,8 @@ int siftmi_stage_blur_ex(int32_t dev, const void *in, int32_t in_dtype, float *o
     const size_t N = (size_t)W * H;
     DevBuf a, b, t, dt, mm;
     if ((rc = a.upload(in, N * esz)) || (rc = b.alloc(N * 4)) || (rc = t.alloc(N * 4)) || (rc = mm.alloc(8))) return rc;
-    Taps tp; tp.n = ntaps;
-    for (int i = 0; i < ntaps; i++) tp.t[i] = taps[i];
-    if ((rc = dt.upload(tp.t, sizeof tp.t))) return rc;
-    tp.dev = dt.as<float>();
+    Taps tp;
+    if ((rc = stage_taps(taps, ntaps, dt, tp))) return rc;
     Options opt = g_default_options;
     opt.xcd_map = (xcd_map & 1) ? 1 : 0;
     opt.march_prio = (xcd_map & 2) ? 0 : 2;       // (forced where not off: the stage planes are smaller than the rule's)
@@ -2615,12 +2177,8 @@ int siftmi_stage_blur_ex(int32_t dev, const void *in, int32_t in_dtype, float *o
     uint32_t *mmp = mm.as<uint32_t>();
     if (norm) {
         hipLaunchKernelGGL(minmax_init, dim3(1), dim3(1), 0, 0, mmp);
-        if (in_dtype == SIFTMI_F32) {
-            hipLaunchKernelGGL(minmax_kernel, dim3(grid_for((int64_t)N / 4, 256, 2048)), dim3(256), 0, 0, a.as<float>(), (int64_t)N, mmp);
-        } else {
-            SIFTMI_TYPED_DISPATCH(in_dtype, hipLaunchKernelGGL(minmax_typed_kernel<DT>, dim3(grid_for((int64_t)N / TypedChunk<DT>::PX, 256, 256)), dim3(256), 0, 0,
-                                                               (const void *)a.p, (int64_t)N, mmp));
-        }
+        // up to 2048 workgroups for f32, 256 for a typed frame; no counter block to reset
+        launch_minmax(nullptr, 0, in_dtype, a.p, (int64_t)N, 256, in_dtype == SIFTMI_F32 ? 2048 : 256, mmp, nullptr, 0, -1);
     }
     BlurForm used = BLUR_NONE;
     if (in_dtype != SIFTMI_F32) {
@@ -2658,13 +2216,11 @@ int siftmi_stage_local_maxmin(int32_t dev, const float *blurs, int32_t W, int32_
     BlurPlanes bp;
     for (int s = 0; s < 6; s++) bp.p[s] = b.as<float>() + (size_t)s * N;
     const int border = par->border_dist;
-    if (W > 2 * border && H > 2 * border) {
-        const int rows = extrema_strip_rows(W, H, border);
-        const int nx = (W - 2 * border + 61) / 62, ny = (H - 2 * border + rows - 1) / rows;
-        const float edth = (octsize <= 1) ? par->edge_thresh0 : par->edge_thresh;
-        hipLaunchKernelGGL(extrema_kernel<false>, dim3((unsigned)((nx * ny + 3) / 4)), dim3(256), 0, 0, bp, W, H, border, rows,
-                           contrast_threshold(*par), edth, c.as<float4>(), &cnt.as<Counters>()->n_cand[0], (int)capacity, RefineArgs{}, -1, -1, 1);
-    }
+    // strips by extrema_strip_rows' own default target, nothing to refine into, XCD order on
+    const DetectGeom geo = detect_geometry(W, H, border, 0, 0, -1, -1);
+    if (geo.blocks)
+        launch_extrema(0, false, geo, bp, W, H, border, contrast_threshold(*par), octave_edge_thresh(*par, octsize), c.as<float4>(),
+                       &cnt.as<Counters>()->n_cand[0], (int)capacity, RefineArgs{}, -1, -1, 1);
     if ((rc = stage_end())) return rc;
     Counters hc;
     HIPCHK(hipMemcpy(&hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost));
@@ -2688,9 +2244,8 @@ int siftmi_stage_interp(int32_t dev, const float *blurs, int32_t W, int32_t H, c
     BlurPlanes bp;
     for (int s = 0; s < 6; s++) bp.p[s] = b.as<float>() + (size_t)s * N;
     Counters *dc = cnt.as<Counters>();
-    hipLaunchKernelGGL(refine_kernel, dim3(grid_for(n, 256, 512)), dim3(256), 0, 0, bp, W, H, (const float4 *)c.as<float4>(),
-                       (const int *)&dc->n_cand[0], (int)n, par->peak_thresh, (float)par->init_sigma, k.as<float4>(),
-                       ks.as<int>(), &dc->g_kp[0], (int)n, 0, &dc->c_scale[0][0]);
+    const RefineArgs ra = {par->peak_thresh, (float)par->init_sigma, k.as<float4>(), ks.as<int>(), &dc->g_kp[0], (int)n, 0, &dc->c_scale[0][0]};
+    launch_refine(0, grid_for(n, 256, 512), bp, W, H, c.as<float4>(), &dc->n_cand[0], (int)n, ra);     // (a workgroup per 256 candidates, at most the plan's 512)
     if ((rc = stage_end())) return rc;
     HIPCHK(hipMemcpy(&hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost));
     const int64_t m = hc.g_kp[0];
@@ -2740,25 +2295,13 @@ int siftmi_stage_detect_ex(int32_t dev, const float *blurs, int32_t W, int32_t H
     BlurPlanes bp;
     for (int s = 0; s < 6; s++) bp.p[s] = b.as<float>() + (size_t)s * N;
     Counters *dc = cnt.as<Counters>();
-    if (W > 2 * border && H > 2 * border) {
-        // launch_detect_octave's geometry; a band is marched as a detection area of its own
-        const int use_rows = rows > 0 ? rows : extrema_strip_rows(W, H, border, g_default_options.ext_strips);
-        const int area = band ? y_hi - y_lo : H - 2 * border;
-        const int nx = (W - 2 * border + 61) / 62, ny = (area + use_rows - 1) / use_rows;
-        const int blocks = std::max(1, (nx * ny + 3) / 4);
-        const float edth = (octsize <= 1) ? par->edge_thresh0 : par->edge_thresh;
+    const int yl = band ? y_lo : -1, yh = band ? y_hi : -1;
+    const DetectGeom geo = detect_geometry(W, H, border, rows, g_default_options.ext_strips, yl, yh);
+    if (geo.blocks) {
         const RefineArgs ra = {par->peak_thresh, (float)par->init_sigma, k.as<float4>(), ka.as<int>(), &dc->g_kp[0], (int)kp_capacity, oct, &dc->c_scale[0][0]};
-        const int yl = band ? y_lo : -1, yh = band ? y_hi : -1;
-        if (form == 1) {
-            hipLaunchKernelGGL(extrema_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, 0, bp, W, H, border, use_rows,
-                               contrast_threshold(*par), edth, c.as<float4>(), &dc->n_cand[0], (int)cand_capacity, ra, yl, yh, xcd_map ? 1 : 0);
-        } else {
-            hipLaunchKernelGGL(extrema_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, 0, bp, W, H, border, use_rows,
-                               contrast_threshold(*par), edth, c.as<float4>(), &dc->n_cand[0], (int)cand_capacity, ra, yl, yh, xcd_map ? 1 : 0);
-            hipLaunchKernelGGL(refine_kernel, dim3(512), dim3(256), 0, 0, bp, W, H, (const float4 *)c.as<float4>(),
-                               (const int *)&dc->n_cand[0], (int)cand_capacity, par->peak_thresh, (float)par->init_sigma, k.as<float4>(),
-                               ka.as<int>(), &dc->g_kp[0], (int)kp_capacity, oct, &dc->c_scale[0][0]);
-        }
+        launch_extrema(0, form == 1, geo, bp, W, H, border, contrast_threshold(*par), octave_edge_thresh(*par, octsize), c.as<float4>(),
+                       &dc->n_cand[0], (int)cand_capacity, ra, yl, yh, xcd_map ? 1 : 0);
+        if (form == 0) launch_refine(0, 512, bp, W, H, c.as<float4>(), &dc->n_cand[0], (int)cand_capacity, ra);
     }
     if ((rc = stage_end())) return rc;
     Counters hc;
@@ -2821,33 +2364,19 @@ int siftmi_stage_orientation_ex(int32_t dev, const float *blurs, int32_t W, int3
     if (maps && (rc = stage_maps_scales(kp_scale, n))) return rc;
     int oct;
     if ((rc = stage_octave(octsize, oct))) return rc;
-    const size_t N = (size_t)W * H;
-    DevBuf b, k, ks, o, oa, cnt, gm, om;
-    if ((rc = b.upload(blurs, 6 * N * 4)) || (rc = k.upload(kps, (size_t)n * 16)) || (rc = ks.upload(kp_scale, (size_t)n * 4)) ||
-        (rc = o.alloc((size_t)capacity * 16)) || (rc = oa.alloc((size_t)capacity * 4)) || (rc = cnt.alloc(sizeof(Counters)))) return rc;
-    if (maps && ((rc = gm.alloc(3 * N * 4)) || (rc = om.alloc(3 * N * 4)))) return rc;
+    StageOctave so;
+    DevBuf o, oa, cnt;
+    if ((rc = so.upload(blurs, W, H, oct, kps, kp_scale, n, maps)) || (rc = o.alloc((size_t)capacity * 16)) || (rc = oa.alloc((size_t)capacity * 4)) ||
+        (rc = cnt.alloc(sizeof(Counters)))) return rc;
     Counters hc{};
     hc.g_kp[0] = (int)n;
     HIPCHK(hipMemcpy(cnt.p, &hc, sizeof hc, hipMemcpyHostToDevice));
-    OctaveTable tab;
-    memset(&tab, 0, sizeof tab);
-    tab.base = b.as<float>(); tab.off[oct] = 0; tab.W[oct] = W; tab.H[oct] = H;
-    tab.gmap = gm.as<float>(); tab.omap = om.as<float>();
-    std::vector<int32_t> aux((size_t)n);
-    for (int64_t i = 0; i < n; i++) aux[(size_t)i] = kp_scale[i] | (oct << 8);
-    HIPCHK(hipMemcpy(ks.p, aux.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    if (maps) stage_maps_launch(tab, oct, oct + 1, 0);
+    if (maps) launch_maps_kernel(so.tab, oct, oct + 1, g_default_options.maps_blocks, 0);
     // a workgroup per keypoint below `team_below` keypoints; `blocks` is also the small-group cut, which would override the grid
     const int team_below = (form & 3) == 2 ? (1 << 30) : 0;
     const int grid = blocks > 0 ? blocks : grid_for(n * 64, 256, 1024), small_blocks = blocks > 0 ? blocks : 512;
-    if (maps)
-        hipLaunchKernelGGL(orientation_kernel<true>, dim3(grid), dim3(256), 0, 0, tab,
-                           par->ori_sigma, (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), cnt.as<Counters>(), 0, (int)n,
-                           o.as<float4>(), oa.as<int>(), (int)capacity, team_below, small_blocks);
-    else
-        hipLaunchKernelGGL(orientation_kernel<false>, dim3(grid), dim3(256), 0, 0, tab,
-                           par->ori_sigma, (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), cnt.as<Counters>(), 0, (int)n,
-                           o.as<float4>(), oa.as<int>(), (int)capacity, team_below, small_blocks);
+    launch_orientation(0, maps, grid, 0, so.tab, par->ori_sigma, so.k.as<float4>(), so.ks.as<int>(), cnt.as<Counters>(), 0, (int)n, o.as<float4>(),
+                       oa.as<int>(), (int)capacity, team_below, small_blocks);
     // What the launch arguments select: the kernel takes the workgroup form when its count (here n) is below team_below.
     // The kernel reports nothing back, so this is the kernel's rule applied on the host, not an observation of the launch.
     const int used = ((int)n < team_below ? 2 : 1) | (maps ? 4 : 0);
@@ -2884,38 +2413,20 @@ int siftmi_stage_descriptor_ex(int32_t dev, const float *blurs, int32_t W, int32
     for (int64_t i = 0; i < n; i++) rows_fit = rows_fit && desc_rows_fit(kps[4 * i + 2], octsize);
     if ((kind == 1 || kind == 2) && !rows_fit) return fail(SIFTMI_EINVAL, "a window of the list has R > %d: streaming form only", SIFT_DESC_MAXRAD);
     const int use = kind ? kind : (rows_fit ? 1 : 3);
-    const size_t N = (size_t)W * H;
-    DevBuf b, k, ks, r, gm, om;
-    if ((rc = b.upload(blurs, 6 * N * 4)) || (rc = k.upload(kps, (size_t)n * 16)) || (rc = ks.upload(kp_scale, (size_t)n * 4)) ||
-        (rc = r.alloc((size_t)n * sizeof(KpRecord)))) return rc;
-    if (maps && ((rc = gm.alloc(3 * N * 4)) || (rc = om.alloc(3 * N * 4)))) return rc;
+    StageOctave so;
+    DevBuf r;
+    if ((rc = so.upload(blurs, W, H, oct, kps, kp_scale, n, maps)) || (rc = r.alloc((size_t)n * sizeof(KpRecord)))) return rc;
     // every form writes every record, that of a hole or of a window without samples included: a record it drops shows as 0xa5 bytes
     if (n > 0) HIPCHK(hipMemset(r.p, 0xa5, (size_t)n * sizeof(KpRecord)));
-    OctaveTable tab;
-    memset(&tab, 0, sizeof tab);
-    tab.base = b.as<float>(); tab.off[oct] = 0; tab.W[oct] = W; tab.H[oct] = H;
-    tab.gmap = gm.as<float>(); tab.omap = om.as<float>();
-    std::vector<int32_t> aux((size_t)n);
-    for (int64_t i = 0; i < n; i++) aux[(size_t)i] = kp_scale[i] | (oct << 8);
     int used = 0;
     if (n > 0) {
-        HIPCHK(hipMemcpy(ks.p, aux.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        if (maps) stage_maps_launch(tab, oct, oct + 1, 0);
+        if (maps) launch_maps_kernel(so.tab, oct, oct + 1, g_default_options.maps_blocks, 0);
         // `blocks` is the grid and both of the kernel's count-based cuts; a workgroup per keypoint below `team_below` keypoints
         const int grid = blocks > 0 ? blocks : grid_for(n, 4, 2048), cut = blocks > 0 ? blocks : (1 << 30);
         const int team_below = use == 2 ? (1 << 30) : 0;
-        if (use == 3)
-            hipLaunchKernelGGL(descriptor_stream_kernel, dim3(grid), dim3(256), 0, 0, tab,
-                               (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), (Counters *)nullptr, 0, 0, (int)n,
-                               (int)n, r.as<KpRecord>(), (int)n, (KpRecord *)nullptr, 0);
-        else if (maps)
-            hipLaunchKernelGGL(descriptor_kernel<true>, dim3(grid), dim3(256), 0, 0, tab,
-                               (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), (Counters *)nullptr, 0, 0, (int)n,
-                               (int)n, r.as<KpRecord>(), (int)n, (KpRecord *)nullptr, 0, team_below, 0, cut, cut);
-        else
-            hipLaunchKernelGGL(descriptor_kernel<false>, dim3(grid), dim3(256), 0, 0, tab,
-                               (const float4 *)k.as<float4>(), (const int *)ks.as<int>(), (Counters *)nullptr, 0, 0, (int)n,
-                               (int)n, r.as<KpRecord>(), (int)n, (KpRecord *)nullptr, 0, team_below, 0, cut, cut);
+        // no counters: the keypoints [0, n) into records [0, n), no pinned copy, no dynamic hand-out
+        launch_descriptors(0, use == 3 ? DESC_STREAM : (maps ? DESC_ROWS_MAPS : DESC_ROWS), grid, 0, so.tab, so.k.as<float4>(), so.ks.as<int>(), nullptr, 0,
+                           0, (int)n, (int)n, r.as<KpRecord>(), (int)n, nullptr, 0, team_below, 0, cut, cut);
         // what the launch selects (the kernel's own rule, count < team_below, applied here: the kernel reports nothing back)
         used = (use == 3 ? 3 : ((int)n < team_below ? 2 : 1)) | (maps ? 4 : 0);
     }
@@ -2945,7 +2456,7 @@ int siftmi_stage_gradient_maps(int32_t dev, const float *planes, int32_t n_oct, 
     DevBuf b, gm, om;
     if ((rc = b.upload(planes, total * 4)) || (rc = gm.upload(gmap, total / 2 * 4)) || (rc = om.upload(omap, total / 2 * 4))) return rc;
     tab.base = b.as<float>(); tab.gmap = gm.as<float>(); tab.omap = om.as<float>();
-    stage_maps_launch(tab, oct_lo, oct_hi, blocks);
+    launch_maps_kernel(tab, oct_lo, oct_hi, blocks > 0 ? blocks : g_default_options.maps_blocks, 0);      // blocks: width of the grid stride (0: the plan's default)
     if ((rc = stage_end())) return rc;
     HIPCHK(hipMemcpy(gmap, gm.p, total / 2 * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(omap, om.p, total / 2 * 4, hipMemcpyDeviceToHost));
@@ -2970,18 +2481,9 @@ int siftmi_stage_convert(int32_t dev, const void *in, int32_t dt, float *out, in
     if (dtype_size(dt) == 0) return fail(SIFTMI_EINVAL, "invalid input format (%d)", dt);
     DevBuf a, o;
     if ((rc = a.upload(in, N * dtype_size(dt))) || (rc = o.alloc(N * 4))) return rc;
-    const int g = grid_for((int64_t)N, 256, 4096);
-    switch (dt) {
-        case SIFTMI_F32: HIPCHK(hipMemcpy(o.p, a.p, N * 4, hipMemcpyDeviceToDevice)); break;
-        case SIFTMI_U8: hipLaunchKernelGGL(convert_kernel<uint8_t>, dim3(g), dim3(256), 0, 0, a.as<uint8_t>(), o.as<float>(), (int64_t)N); break;
-        case SIFTMI_U16: hipLaunchKernelGGL(convert_kernel<uint16_t>, dim3(g), dim3(256), 0, 0, a.as<uint16_t>(), o.as<float>(), (int64_t)N); break;
-        case SIFTMI_U32: hipLaunchKernelGGL(convert_kernel<uint32_t>, dim3(g), dim3(256), 0, 0, a.as<uint32_t>(), o.as<float>(), (int64_t)N); break;
-        case SIFTMI_U64: hipLaunchKernelGGL(convert_kernel<uint64_t>, dim3(g), dim3(256), 0, 0, a.as<uint64_t>(), o.as<float>(), (int64_t)N); break;
-        case SIFTMI_I32: hipLaunchKernelGGL(convert_kernel<int32_t>, dim3(g), dim3(256), 0, 0, a.as<int32_t>(), o.as<float>(), (int64_t)N); break;
-        case SIFTMI_I64: hipLaunchKernelGGL(convert_kernel<int64_t>, dim3(g), dim3(256), 0, 0, a.as<int64_t>(), o.as<float>(), (int64_t)N); break;
-        case SIFTMI_F64: hipLaunchKernelGGL(convert_kernel<double>, dim3(g), dim3(256), 0, 0, a.as<double>(), o.as<float>(), (int64_t)N); break;
-        case SIFTMI_RGB8: hipLaunchKernelGGL(convert_rgb_kernel, dim3(g), dim3(256), 0, 0, a.as<uint8_t>(), o.as<float>(), (int64_t)N); break;
-    }
+    // (an f32 frame is copied: the plan never converts one)
+    if (dt == SIFTMI_F32) HIPCHK(hipMemcpy(o.p, a.p, N * 4, hipMemcpyDeviceToDevice));
+    else launch_convert(0, dt, a.p, o.as<float>(), (int64_t)N);
     if ((rc = stage_end())) return rc;
     HIPCHK(hipMemcpy(out, o.p, N * 4, hipMemcpyDeviceToHost));
     return SIFTMI_OK;

@@ -1,5 +1,6 @@
 """dev: basic blocks of one kernel in the device assembly (instruction mix per block):
-   hipcc ... --cuda-device-only -S -o /tmp/dis/siftmi.s sift_pyocl_amd/csrc/siftmi.hip ; python tools/dev/isa_blocks.py /tmp/dis/siftmi.s extrema_kernel [min_len]"""
+   hipcc <the Makefile's FLAGS> --cuda-device-only -S -o /tmp/dis/siftmi.s sift_pyocl_amd/csrc/siftmi.hip ; python tools/dev/isa_blocks.py /tmp/dis/siftmi.s extrema_kernel [min_len]
+(one .s per .hip: the SIFT kernels are in siftmi.hip, the matcher's and the consensus filter's in match.hip; tools/dev/isa_same.py compares two builds)"""
 import sys, collections
 lines = open(sys.argv[1]).read().split("\n")
 key = sys.argv[2]; min_len = int(sys.argv[3]) if len(sys.argv) > 3 else 25
