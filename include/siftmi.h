@@ -230,6 +230,23 @@ int siftmi_match_set_roi(siftmi_matcher *m, const int8_t *roi, int32_t roi_width
 int siftmi_match_ex(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t roi_mode,
                     int32_t mutual, int32_t *pairs, int64_t capacity, int64_t *n_out, int64_t *n_total);
+/* Windowed matching (extension; DESIGN.md section 7 row 6, restated in numpy by tests/window_ref.py): the rule of `matching`
+ * (matching_cpu.cl:57-109) applied only to the CANDIDATES of a list-1 keypoint i, the list-2 keypoints j with
+ *     fabsf((x2[j] - x1[i]) - sx) <= wx  &&  fabsf((y2[j] - y1[i]) - sy) <= wy          (f32, unfused; a NaN makes it false)
+ * taken in ascending j: strict '<' (the earliest index of the minimum wins, dist2 is the second smallest of the multiset),
+ * pair kept iff dist2 != 0 && dist1 / dist2 < ratio_th with both distances starting at 1e12f.  A keypoint without a candidate
+ * pairs with nothing; a keypoint with exactly one candidate always pairs with it.  wx / wy may be +inf (every finite
+ * difference is admitted: with a zero shift and finite coordinates the result is siftmi_match's).
+ *   mutual       keep (i, j) only if i is also the nearest candidate of j (same predicate, same operand order), ties to the
+ *                smallest i
+ * Capacity, SIFTMI_ECAPACITY, *n_out / *n_total, siftmi_match_last_kernel_ms (all kernels of the call, the binning of the
+ * lists included) and the four siftmi_match_last_stage_ms slots (binning counts as "matching") as for siftmi_match_ex; both
+ * lists are used where they lie.  The region of interest is not consulted.  n1 == 0 or n2 == 0: no pair, SIFTMI_OK.
+ * SIFTMI_EINVAL, nothing launched: a negative or NaN window, a shift that is not finite, a null list with a non-zero count,
+ * a negative count. */
+int siftmi_match_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                        const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, float wx, float wy,
+                        float sx, float sy, int32_t mutual, int32_t *pairs, int64_t capacity, int64_t *n_out, int64_t *n_total);
 /* Consensus filter over the pairs of a match (no reference counterpart: the reference hands this to the third-party
  * feature.sift_orsa, sift-src/alignment.py:54-57, 260-264).  n_hyp affine maps are solved from pseudo-random triples of matches,
  * every match votes for every map that brings its list-1 position within `tol` pixels of its list-2 position, the map with most

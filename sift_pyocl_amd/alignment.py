@@ -224,7 +224,7 @@ class LinearAlign(object):
 
     # ------------------------------------------------------------------ public entry
     def align(self, img, shift_only=False, return_all=False, double_check=False, relative=False, orsa=False,
-              robust=False, robust_tol=3.0, robust_hyp=2048):
+              robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None):
         """Align `img` on the reference image.
 
         :param img: image to align (same shape as the reference)
@@ -238,6 +238,12 @@ class LinearAlign(object):
                        act on those.  ``return_all`` gains the key ``"inliers"``, the boolean mask over ``"matching"``.
         :param robust_tol: distance in pixels within which a match agrees with a candidate map
         :param robust_hyp: number of candidate maps tried
+        :param max_shift: (extension) None, or a bound in pixels on how far a keypoint of `img` lies from its partner in the
+                       reference frame, a scalar or an (x, y) pair: the matcher then compares each reference keypoint only with
+                       the keypoints within that window (``MatchPlan.match(window=max_shift)``), which is many times faster on
+                       dense frames; everything after the match is unchanged.  When the true displacement exceeds ``max_shift``
+                       the true partners are not candidates: expect few or wrong matches, not an error.  On sparse frames a
+                       keypoint with a single candidate always pairs with it; ``robust=True`` is recommended there.
         :return: the aligned image, the dict, or None when no keypoint matches
         """
         logger.debug("ref_keypoints: %s" % self.ref_kp.size)
@@ -247,7 +253,7 @@ class LinearAlign(object):
             logger.debug("mod image keypoints: %s" % kp.size)
             # both lists are matched where they lie in HBM: the reference list uploaded once, the new one still in the plan
             ref_list = self.ref_kp if self._ref_dev is None else self._ref_dev
-            pairs = self.match.match(ref_list, self.sift.device_records() if kp.size else kp, raw_results=True)
+            pairs = self.match.match(ref_list, self.sift.device_records() if kp.size else kp, raw_results=True, window=max_shift)
             n_pairs = pairs.shape[0]
             if n_pairs == 0:
                 logger.warning("No matching keypoints")

@@ -1,11 +1,12 @@
-// match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp) and the consensus filter over its
-// pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
+// (k_match_window.hpp) and the consensus filter over the pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstring>
 #include <new>
 
 #include "host_common.hpp"
 #include "k_match.hpp"
+#include "k_match_window.hpp"
 #include "k_consensus.hpp"
 
 using namespace siftk;
@@ -46,6 +47,14 @@ struct siftmi_matcher {
     int64_t cap_c_pts = 0, cap_c_mask = 0, cap_c_valid = 0, cap_c_models = 0, cap_c_votes = 0;
     ConsensusResult *c_result = nullptr;
     hipEvent_t ec_a = nullptr, ec_b = nullptr;
+    // windowed matching (siftmi_match_window): header + two histograms + two scans over the cells, the work list, the dense
+    // cell-sorted copy of the list (descriptors; x, y, original index) and the queries' order; grown on demand
+    int *w_cells = nullptr;
+    int2 *w_work = nullptr;
+    uint4 *w_desc = nullptr;
+    float4 *w_meta = nullptr;
+    int *w_order = nullptr;
+    int64_t cap_w_cells = 0, cap_w_work = 0, cap_w_desc = 0, cap_w_meta = 0, cap_w_order = 0;
 };
 
 namespace {
@@ -103,7 +112,8 @@ int siftmi_match_destroy(siftmi_matcher *m) {
     if (m->pairs) hipFree(m->pairs);
     if (m->partial) hipFree(m->partial);
     for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
-                    (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result})
+                    (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result,
+                    (void *)m->w_cells, (void *)m->w_work, (void *)m->w_desc, (void *)m->w_meta, (void *)m->w_order})
         if (q) hipFree(q);
     if (m->ec_a) hipEventDestroy(m->ec_a);
     if (m->ec_b) hipEventDestroy(m->ec_b);
@@ -252,6 +262,120 @@ int siftmi_match(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int3
                  const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, int32_t *pairs,
                  int64_t capacity, int64_t *n_out, int64_t *n_total) {
     return siftmi_match_ex(m, kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, ratio_th, 0, 0, pairs, capacity, n_out, n_total);
+}
+
+// Windowed matching (k_match_window.hpp; the contract is DESIGN.md section 7 row 6).  Both lists are used where they lie.
+namespace {
+constexpr int64_t MW_CELL_WORDS = SIFT_MW_HDR + 4 * (int64_t)(SIFT_MW_MAXCELLS + 1);
+// work items of `nq` queries at most: a cell's last chunk may be partial, and only a cell with a query has one
+int64_t mw_work_cap(int64_t nq) { return nq / SIFT_MW_QB + (nq < SIFT_MW_MAXCELLS ? nq : SIFT_MW_MAXCELLS) + 1; }
+
+int mw_ensure(siftmi_matcher *m, int64_t n1, int64_t n2, bool both) {
+    const int64_t nl = both ? (n1 > n2 ? n1 : n2) : n2, nq = both ? nl : n1;
+    int rc;
+    if ((rc = ensure((void **)&m->w_cells, &m->cap_w_cells, MW_CELL_WORDS, sizeof(int))) ||
+        (rc = ensure((void **)&m->w_work, &m->cap_w_work, mw_work_cap(nq), sizeof(int2))) ||
+        (rc = ensure((void **)&m->w_desc, &m->cap_w_desc, nl * 8, sizeof(uint4))) ||
+        (rc = ensure((void **)&m->w_meta, &m->cap_w_meta, nl, sizeof(float4))) ||
+        (rc = ensure((void **)&m->w_order, &m->cap_w_order, nq, sizeof(int)))) return rc;
+    return SIFTMI_OK;
+}
+
+// one direction of the windowed scan: `nq` queries against the candidates among `nl` list elements (the scratch is sized by
+// mw_ensure).  reverse: the queries are list-2 keypoints; the predicate keeps (x2 - x1) - sx, so their window centre is x2 - sx.
+int match_window_direction(siftmi_matcher *m, const uint8_t *dq, int64_t nq, const uint8_t *dl, int64_t nl, int reverse, float wx, float wy,
+                           float sx, float sy, float ratio_th, int2 *pairs, int cap, int *nearest) {
+    uint32_t *hdr = (uint32_t *)m->w_cells;
+    int *cnt_l = m->w_cells + SIFT_MW_HDR, *cnt_q = cnt_l + SIFT_MW_MAXCELLS + 1;
+    int *start_l = cnt_q + SIFT_MW_MAXCELLS + 1, *start_q = start_l + SIFT_MW_MAXCELLS + 1;
+    const float cx = reverse ? -sx : sx, cy = reverse ? -sy : sy;
+    const int work_cap = (int)mw_work_cap(nq);
+    const dim3 bl((unsigned)((nl + 255) / 256)), bq((unsigned)((nq + 255) / 256));
+    // minima start at 0xffffffff, maxima, the work count and both histograms at 0
+    HIPCHK(hipMemsetAsync(hdr, 0xff, 2 * sizeof(uint32_t), m->stream));
+    HIPCHK(hipMemsetAsync(hdr + 2, 0, (size_t)(SIFT_MW_HDR - 2 + 2 * (SIFT_MW_MAXCELLS + 1)) * sizeof(int), m->stream));
+    hipLaunchKernelGGL(mw_extent_kernel, bl, dim3(256), 0, m->stream, dl, (int)nl, hdr);
+    hipLaunchKernelGGL(mw_count_kernel, bl, dim3(256), 0, m->stream, dl, (int)nl, (const uint32_t *)hdr, wx, wy, 0.f, 0.f, cnt_l);
+    hipLaunchKernelGGL(mw_count_kernel, bq, dim3(256), 0, m->stream, dq, (int)nq, (const uint32_t *)hdr, wx, wy, cx, cy, cnt_q);
+    hipLaunchKernelGGL(mw_scan_kernel, dim3(1), dim3(1024), 0, m->stream, hdr, wx, wy, cnt_l, cnt_q, start_l, start_q, m->w_work, work_cap);
+    hipLaunchKernelGGL(mw_scatter_list_kernel, dim3((unsigned)((nl * 8 + 255) / 256)), dim3(256), 0, m->stream, dl, (int)nl,
+                       (const uint32_t *)hdr, wx, wy, cnt_l, m->w_desc, m->w_meta);
+    hipLaunchKernelGGL(mw_scatter_query_kernel, bq, dim3(256), 0, m->stream, dq, (int)nq, (const uint32_t *)hdr, wx, wy, cx, cy, cnt_q, m->w_order);
+    hipLaunchKernelGGL(mw_match_kernel, dim3((unsigned)work_cap), dim3(256), 0, m->stream, dq, (int)nq, (int)nl, (const uint32_t *)hdr,
+                       wx, wy, sx, sy, reverse, (const int *)start_l, (const int *)start_q, (const int *)m->w_order, (const int2 *)m->w_work,
+                       (const uint4 *)m->w_desc, (const float4 *)m->w_meta, ratio_th, pairs, m->counter, cap, nearest);
+    return SIFTMI_OK;
+}
+}  // namespace
+
+int siftmi_match_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                        const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, float wx, float wy,
+                        float sx, float sy, int32_t mutual, int32_t *pairs, int64_t capacity, int64_t *n_out, int64_t *n_total) {
+    if (!m || !n_out) return fail(SIFTMI_EINVAL, "null argument");
+    if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff / 8 || n2 > 0x7fffffff / 8) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (!(wx >= 0.f) || !(wy >= 0.f)) return fail(SIFTMI_EINVAL, "the window must be >= 0 (it may be infinite), not (%g, %g)", wx, wy);
+    if (!std::isfinite(sx) || !std::isfinite(sy)) return fail(SIFTMI_EINVAL, "the window shift must be finite, not (%g, %g)", sx, sy);
+    HIPCHK(hipSetDevice(m->device));
+    *n_out = 0;
+    if (n_total) *n_total = 0;
+    for (float &v : m->stage_ms) v = -1.f;
+    if (n1 == 0 || n2 == 0) return SIFTMI_OK;   // no candidate: dist1 == dist2 == 1e12 -> ratio 1, never < ratio_th
+    if (kp1_is_device || kp2_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    int rc;
+    const bool prof = m->profile && m->ev[0];
+    if (prof) hipEventRecord(m->ev[0], m->stream);
+    if (!kp1_is_device && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (prof) hipEventRecord(m->ev[1], m->stream);
+    if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (prof) hipEventRecord(m->ev[2], m->stream);
+    int64_t cap = m->size;                      // as siftmi_match_ex: max(size, min(n1, n2))
+    if ((n1 < n2 ? n1 : n2) > cap) cap = (n1 < n2 ? n1 : n2);
+    if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, cap, sizeof(int2))) || (rc = mw_ensure(m, n1, n2, mutual != 0))) return rc;
+    if (mutual && ((rc = ensure((void **)&m->nearest, &m->cap_nearest, n2, sizeof(int))) ||
+                   (rc = ensure((void **)&m->pairs2, &m->cap_pairs2, cap, sizeof(int2))))) return rc;
+    HIPCHK(hipMemsetAsync(m->counter, 0, 8, m->stream));
+    hipEventRecord(m->ea, m->stream);
+    if ((rc = match_window_direction(m, d1, n1, d2, n2, 0, wx, wy, sx, sy, ratio_th, m->pairs, (int)cap, nullptr))) return rc;
+    int2 *result = m->pairs;
+    int *result_counter = m->counter;
+    if (mutual) {
+        // reverse scan: the nearest candidate among list 1 of every list-2 keypoint, then the filter over the forward pairs
+        if ((rc = match_window_direction(m, d2, n2, d1, n1, 1, wx, wy, sx, sy, ratio_th, nullptr, 0, m->nearest))) return rc;
+        hipLaunchKernelGGL(mw_mutual_filter_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, m->stream, (const int2 *)m->pairs,
+                           (const int *)m->counter, (int)cap, (const int *)m->nearest, (int)n2, m->pairs2, m->counter + 1);
+        result = m->pairs2; result_counter = m->counter + 1;
+    }
+    hipEventRecord(m->eb, m->stream);
+    int count = 0;
+    HIPCHK(hipMemcpyAsync(&count, result_counter, 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    hipEventElapsedTime(&m->last_ms, m->ea, m->eb);
+    if (n_total) *n_total = count;
+    int64_t n = count < cap ? count : cap;
+    rc = SIFTMI_OK;
+    if (n > capacity) { n = capacity; rc = SIFTMI_ECAPACITY; g_err = "pair capacity too small; result truncated"; }
+    if (prof) {
+        m->stage_ms[2] = m->last_ms;
+        if (!kp1_is_device) hipEventElapsedTime(&m->stage_ms[0], m->ev[0], m->ev[1]);
+        if (!kp2_is_device) hipEventElapsedTime(&m->stage_ms[1], m->ev[1], m->ev[2]);
+    }
+    if (n > 0) {
+        if (!pairs) return fail(SIFTMI_EINVAL, "null pairs buffer");
+        if (prof) {
+            hipEventRecord(m->ev[3], m->stream);
+            HIPCHK(hipMemcpyAsync(pairs, result, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost, m->stream));
+            hipEventRecord(m->ev[4], m->stream);
+            HIPCHK(hipStreamSynchronize(m->stream));
+            hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
+        } else {
+            HIPCHK(hipMemcpy(pairs, result, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+        }
+    }
+    *n_out = n;
+    return rc;
 }
 
 // Consensus filter over the pairs of a match (k_consensus.hpp; the contract is DESIGN.md section 7 row 5).  The lists and the

@@ -70,7 +70,7 @@ class MatchPlan(object):
 
     ROI_MODES = {0: 0, None: 0, False: 0, "off": 0, 1: 1, True: 1, "reference": 1, "matching_valid": 1, 2: 2, "strict": 2}
 
-    def match(self, nkp1, nkp2, raw_results=False, roi_mode=0, mutual=False):
+    def match(self, nkp1, nkp2, raw_results=False, roi_mode=0, mutual=False, window=None, window_shift=(0.0, 0.0)):
         """Calculate the matching of 2 keypoint lists
 
         :param nkp1, nkp2: numpy 1D recarray of keypoints (or device tensors of 144-byte records)
@@ -79,6 +79,18 @@ class MatchPlan(object):
                          reaches its ``matching_valid`` kernel; "reference" / 1 runs that kernel's semantics literally
                          (matching_cpu.cl:136-199); "strict" / 2 drops every keypoint that is not on a non-zero pixel
         :param mutual: keep only pairs that are nearest neighbours in both directions (extension)
+        :param window: (extension) None, or the half width of a search window in pixels, a scalar or an ``(wx, wy)`` pair (x first,
+                       like the record fields; ``inf`` is allowed).  Keypoint j of the second list is then a *candidate* of keypoint
+                       i of the first iff ``abs((x2[j] - x1[i]) - sx) <= wx and abs((y2[j] - y1[i]) - sy) <= wy`` (float32), and
+                       the reference's rule -- nearest and second nearest descriptor, ratio test -- sees the candidates only
+                       (DESIGN.md section 7 row 6).  For lists whose partners are known to lie within a few pixels of each other
+                       this compares a few hundred descriptors per keypoint instead of the whole list.  Consequences of the
+                       rule: a keypoint without a candidate pairs with nothing; a keypoint with exactly ONE candidate always
+                       pairs with it (the second distance keeps its initial 1e12, as in the reference when the second list has
+                       one element), so a small window on sparse lists returns such lone-candidate pairs: ``mutual=True`` and
+                       ``consensus()`` are the filters for those.  With ``mutual``, i must also be the nearest candidate of j.
+                       Not defined together with ``roi_mode``.
+        :param window_shift: ``(sx, sy)``, the expected displacement of the second list against the first (centre of the window)
         """
         assert len(nkp1.shape) == 1
         assert len(nkp2.shape) == 1
@@ -96,8 +108,17 @@ class MatchPlan(object):
             mode = self.ROI_MODES[roi_mode]
             if mode and self.roi is None:
                 raise RuntimeError("roi_mode=%r needs a region of interest (set_roi)" % (roi_mode,))
-            _lib.check(L.siftmi_match_ex(self._handle, p1, n1, dev1, p2, n2, dev2, C.c_float(ratio), mode, int(bool(mutual)),
-                                         pairs.ctypes.data, cap, C.byref(n), C.byref(total)), allow=(_lib.ECAPACITY,))
+            if window is None:
+                _lib.check(L.siftmi_match_ex(self._handle, p1, n1, dev1, p2, n2, dev2, C.c_float(ratio), mode, int(bool(mutual)),
+                                             pairs.ctypes.data, cap, C.byref(n), C.byref(total)), allow=(_lib.ECAPACITY,))
+            else:
+                if mode:
+                    raise RuntimeError("window= together with roi_mode=%r is not defined" % (roi_mode,))
+                wx, wy = (window if hasattr(window, "__len__") else (window, window))
+                sx, sy = window_shift
+                _lib.check(L.siftmi_match_window(self._handle, p1, n1, dev1, p2, n2, dev2, C.c_float(ratio), C.c_float(wx), C.c_float(wy),
+                                                 C.c_float(sx), C.c_float(sy), int(bool(mutual)), pairs.ctypes.data, cap,
+                                                 C.byref(n), C.byref(total)), allow=(_lib.ECAPACITY,))
             size = int(n.value)
             if self.profile:             # match.py:226-263: (label, event) pairs of this call, appended until reset_timer()
                 self.events += self._stage_events()
