@@ -209,7 +209,9 @@ int siftmi_batch_fetch(siftmi_batch *batch, siftmi_keypoint *out, int32_t out_is
  * siftmi_match        <- MatchPlan.match (match.py:200-271) with the `matching` kernel
  *                        (matching_cpu.cl:57-109): L1 distance, best/second-best, ratio test
  *                        dist1/dist2 < ratio_th.  *n_out = pairs written (<= capacity); *n_total = pairs
- *                        that passed (the reference silently drops the excess, match.py:252).
+ *                        that passed (the reference silently drops the excess, match.py:252).  The device keeps
+ *                        at most `size` pairs of a call; a call with min(n1, n2) > size raises the matcher's
+ *                        size to it for good, as the reference's kpsize grows (match.py:241-243).
  */
 int siftmi_match_create(int64_t size, int32_t device_id, int32_t profile, siftmi_matcher **out);
 int siftmi_match(siftmi_matcher *plan, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,

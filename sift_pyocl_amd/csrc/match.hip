@@ -189,9 +189,9 @@ int siftmi_match_ex(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, i
     if (prof) hipEventRecord(m->ev[1], m->stream);
     if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
     if (prof) hipEventRecord(m->ev[2], m->stream);
-    // match.py:241-243,252: output capacity = max(self.kpsize, min(n1, n2))
-    int64_t cap = m->size;
-    if ((n1 < n2 ? n1 : n2) > cap) cap = (n1 < n2 ? n1 : n2);
+    // match.py:241-243,252: kpsize grows to min(n1, n2) and stays grown; the output capacity is kpsize
+    if ((n1 < n2 ? n1 : n2) > m->size) m->size = (n1 < n2 ? n1 : n2);
+    const int64_t cap = m->size;
     if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, cap, sizeof(int2)))) return rc;
     HIPCHK(hipMemsetAsync(m->counter, 0, 8, m->stream));
     hipEventRecord(m->ea, m->stream);
@@ -330,8 +330,8 @@ int siftmi_match_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n
     if (prof) hipEventRecord(m->ev[1], m->stream);
     if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
     if (prof) hipEventRecord(m->ev[2], m->stream);
-    int64_t cap = m->size;                      // as siftmi_match_ex: max(size, min(n1, n2))
-    if ((n1 < n2 ? n1 : n2) > cap) cap = (n1 < n2 ? n1 : n2);
+    if ((n1 < n2 ? n1 : n2) > m->size) m->size = (n1 < n2 ? n1 : n2);      // as siftmi_match_ex: the size grows to min(n1, n2)
+    const int64_t cap = m->size;
     if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, cap, sizeof(int2))) || (rc = mw_ensure(m, n1, n2, mutual != 0))) return rc;
     if (mutual && ((rc = ensure((void **)&m->nearest, &m->cap_nearest, n2, sizeof(int))) ||
                    (rc = ensure((void **)&m->pairs2, &m->cap_pairs2, cap, sizeof(int2))))) return rc;
