@@ -249,6 +249,22 @@ int siftmi_match_ex(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, i
 int siftmi_match_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
                         const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, float ratio_th, float wx, float wy,
                         float sx, float sy, int32_t mutual, int32_t *pairs, int64_t capacity, int64_t *n_out, int64_t *n_total);
+/* k nearest neighbours WITH their descriptor distances (extension; DESIGN.md section 7 row 7, restated in numpy by tests/knn_ref.py).
+ * d(i, j) is the int32 L1 distance over the 128 descriptor bytes (0 .. 32 640).  Row i of the result holds the k smallest elements
+ * of {(d(i, j), j) : 0 <= j < n2} in ascending lexicographic order of (distance, index): among equal distances the smaller index
+ * comes first.  idx_out[i * k + r] is the index and dist_out[i * k + r] the distance; where n2 < k the remaining slots hold -1 / -1.
+ * The order is total: the result does not depend on partitioning or scheduling.  Positions, the region of interest and the ratio
+ * play no part.  idx[, 0], dist[, 0], dist[, 1] are the best / dist1 / dist2 of `matching` (matching_cpu.cl:57-109).
+ *   k            1 .. 8
+ *   idx_out, dist_out   host, n1 * k int32 each
+ * Both lists are used where they lie (host lists are staged).  n1 == 0 writes nothing, n2 == 0 writes -1 everywhere; neither
+ * launches anything.  The call leaves the matcher's pair capacity (`size`) alone.  siftmi_match_last_kernel_ms then reports the two
+ * knn kernels and siftmi_match_last_stage_ms the call's stages: [0], [1] the list copies, [2] the kernels, [3] the copy of the result.
+ * SIFTMI_EINVAL, nothing written, nothing launched: k outside 1 .. 8, a negative count, a null list or result buffer with a
+ * non-zero count. */
+int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k,
+                     int32_t *idx_out, int32_t *dist_out);
 /* Consensus filter over the pairs of a match (no reference counterpart: the reference hands this to the third-party
  * feature.sift_orsa, sift-src/alignment.py:54-57, 260-264).  n_hyp affine maps are solved from pseudo-random triples of matches,
  * every match votes for every map that brings its list-1 position within `tol` pixels of its list-2 position, the map with most

@@ -7,8 +7,8 @@ kernels for gfx950 reached through a C ABI (include/siftmi.h).
 version = "0.1"
 from .param import par
 from .plan import SiftPlan
-from .match import MatchPlan
+from .match import MatchPlan, ratio_filter
 from .alignment import LinearAlign
 from .batch import BatchPlan
 
-__all__ = ["par", "SiftPlan", "MatchPlan", "LinearAlign", "BatchPlan", "version"]
+__all__ = ["par", "SiftPlan", "MatchPlan", "ratio_filter", "LinearAlign", "BatchPlan", "version"]

@@ -1,5 +1,5 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp) and the consensus filter over the pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scan that returns distances (k_knn.hpp) and the consensus filter over the pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -7,6 +7,7 @@
 #include "host_common.hpp"
 #include "k_match.hpp"
 #include "k_match_window.hpp"
+#include "k_knn.hpp"
 #include "k_consensus.hpp"
 
 using namespace siftk;
@@ -55,6 +56,10 @@ struct siftmi_matcher {
     float4 *w_meta = nullptr;
     int *w_order = nullptr;
     int64_t cap_w_cells = 0, cap_w_work = 0, cap_w_desc = 0, cap_w_meta = 0, cap_w_order = 0;
+    // k nearest neighbours (siftmi_match_knn): the partitions' keys and the result (n1 * k indices, then n1 * k distances); grown on demand
+    uint32_t *knn_keys = nullptr;
+    int32_t *knn_out = nullptr;
+    int64_t cap_knn_keys = 0, cap_knn_out = 0;
 };
 
 namespace {
@@ -113,7 +118,8 @@ int siftmi_match_destroy(siftmi_matcher *m) {
     if (m->partial) hipFree(m->partial);
     for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
                     (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result,
-                    (void *)m->w_cells, (void *)m->w_work, (void *)m->w_desc, (void *)m->w_meta, (void *)m->w_order})
+                    (void *)m->w_cells, (void *)m->w_work, (void *)m->w_desc, (void *)m->w_meta, (void *)m->w_order,
+                    (void *)m->knn_keys, (void *)m->knn_out})
         if (q) hipFree(q);
     if (m->ec_a) hipEventDestroy(m->ec_a);
     if (m->ec_b) hipEventDestroy(m->ec_b);
@@ -376,6 +382,97 @@ int siftmi_match_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n
     }
     *n_out = n;
     return rc;
+}
+
+// k nearest neighbours with their distances (k_knn.hpp; the contract is DESIGN.md section 7 row 7).
+namespace {
+// the decomposition of match_direction: query blocks x partitions of the list, about 2048 workgroups, a partition a whole number
+// of tiles and at most SIFT_MATCH_MAX_PART elements
+void knn_partitions(int64_t nq, int64_t nl, int *qblocks, int *nparts, int *part_len) {
+    *qblocks = (int)((nq + 256 * SIFT_MATCH_QPT - 1) / (256 * SIFT_MATCH_QPT));
+    int np = (2048 + *qblocks - 1) / *qblocks;
+    const int max_parts = (int)((nl + 4 * SIFT_MATCH_TILE - 1) / (4 * SIFT_MATCH_TILE));
+    if (np > max_parts) np = max_parts;
+    const int min_parts = (int)((nl + SIFT_MATCH_MAX_PART - 1) / SIFT_MATCH_MAX_PART);     // 16-bit index inside a partition
+    if (np < min_parts) np = min_parts;
+    if (np < 1) np = 1;
+    int len = (int)((nl + np - 1) / np);
+    len = (len + SIFT_MATCH_TILE - 1) / SIFT_MATCH_TILE * SIFT_MATCH_TILE;
+    *part_len = len;
+    *nparts = (int)((nl + len - 1) / len);
+}
+// the instance a requested k (1 .. SIFT_KNN_MAX) runs on: the next of 1, 2, 4, 8
+int knn_instance(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
+
+void launch_knn_partial(hipStream_t st, int K, dim3 grid, const uint8_t *dq, int nq, const uint8_t *dl, int nl, int part_len, uint32_t *keys) {
+    switch (K) {
+    case 1: hipLaunchKernelGGL(knn_partial_kernel<1>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    case 2: hipLaunchKernelGGL(knn_partial_kernel<2>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    case 4: hipLaunchKernelGGL(knn_partial_kernel<4>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    default: hipLaunchKernelGGL(knn_partial_kernel<8>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    }
+}
+void launch_knn_merge(hipStream_t st, int K, const uint32_t *keys, int nq, int nparts, int part_len, int k, int32_t *idx, int32_t *dist) {
+    const dim3 grid((unsigned)((nq + 255) / 256));
+    switch (K) {
+    case 1: hipLaunchKernelGGL(knn_merge_kernel<1>, grid, dim3(256), 0, st, keys, nq, nparts, part_len, k, idx, dist); break;
+    case 2: hipLaunchKernelGGL(knn_merge_kernel<2>, grid, dim3(256), 0, st, keys, nq, nparts, part_len, k, idx, dist); break;
+    case 4: hipLaunchKernelGGL(knn_merge_kernel<4>, grid, dim3(256), 0, st, keys, nq, nparts, part_len, k, idx, dist); break;
+    default: hipLaunchKernelGGL(knn_merge_kernel<8>, grid, dim3(256), 0, st, keys, nq, nparts, part_len, k, idx, dist); break;
+    }
+}
+}  // namespace
+
+int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k,
+                     int32_t *idx_out, int32_t *dist_out) {
+    if (!m) return fail(SIFTMI_EINVAL, "null argument");
+    if (k < 1 || k > SIFT_KNN_MAX) return fail(SIFTMI_EINVAL, "k must be 1 .. %d, not %d", SIFT_KNN_MAX, k);
+    if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n1 > 0 && (!idx_out || !dist_out)) return fail(SIFTMI_EINVAL, "null result buffer");
+    HIPCHK(hipSetDevice(m->device));
+    for (float &v : m->stage_ms) v = -1.f;
+    m->last_ms = 0;
+    if (n1 == 0) return SIFTMI_OK;
+    const size_t cells = (size_t)n1 * (size_t)k;
+    if (n2 == 0) {                              // no neighbour at all: nothing is launched
+        for (size_t t = 0; t < cells; t++) { idx_out[t] = -1; dist_out[t] = -1; }
+        return SIFTMI_OK;
+    }
+    if (kp1_is_device || kp2_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    int rc;
+    const bool prof = m->profile && m->ev[0];
+    if (prof) hipEventRecord(m->ev[0], m->stream);
+    if (!kp1_is_device && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (prof) hipEventRecord(m->ev[1], m->stream);
+    if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (prof) hipEventRecord(m->ev[2], m->stream);
+    const int K = knn_instance(k);
+    int qblocks, nparts, part_len;
+    knn_partitions(n1, n2, &qblocks, &nparts, &part_len);
+    if ((rc = ensure((void **)&m->knn_keys, &m->cap_knn_keys, (int64_t)nparts * n1 * K, sizeof(uint32_t))) ||
+        (rc = ensure((void **)&m->knn_out, &m->cap_knn_out, 2 * (int64_t)cells, sizeof(int32_t)))) return rc;
+    int32_t *d_idx = m->knn_out, *d_dist = m->knn_out + cells;
+    hipEventRecord(m->ea, m->stream);
+    launch_knn_partial(m->stream, K, dim3((unsigned)qblocks, (unsigned)nparts), d1, (int)n1, d2, (int)n2, part_len, m->knn_keys);
+    launch_knn_merge(m->stream, K, m->knn_keys, (int)n1, nparts, part_len, k, d_idx, d_dist);
+    hipEventRecord(m->eb, m->stream);
+    if (prof) hipEventRecord(m->ev[3], m->stream);
+    HIPCHK(hipMemcpyAsync(idx_out, d_idx, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(dist_out, d_dist, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    if (prof) hipEventRecord(m->ev[4], m->stream);
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    hipEventElapsedTime(&m->last_ms, m->ea, m->eb);
+    if (prof) {
+        m->stage_ms[2] = m->last_ms;
+        if (!kp1_is_device) hipEventElapsedTime(&m->stage_ms[0], m->ev[0], m->ev[1]);
+        if (!kp2_is_device) hipEventElapsedTime(&m->stage_ms[1], m->ev[1], m->ev[2]);
+        hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
+    }
+    return SIFTMI_OK;
 }
 
 // Consensus filter over the pairs of a match (k_consensus.hpp; the contract is DESIGN.md section 7 row 5).  The lists and the

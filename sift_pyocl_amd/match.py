@@ -19,6 +19,33 @@ from .plan import _pointer_of
 logger = logging.getLogger("sift.match")
 
 
+def ratio_filter(idx, dist, ratio=None):
+    """The reference's ratio test (matching_cpu.cl:103-108) on the result of ``MatchPlan.knn`` (extension), with a ratio of the
+    caller's choice: the pairs ``(i, idx[i, 0])`` of the rows with ``dist2 != 0 and dist1 / dist2 < float32(ratio ** 2)`` in
+    float32, where ``dist1, dist2 = dist[i, 0], dist[i, 1]`` and a missing distance (-1) counts as ``1e12f``.  With the default
+    ratio this is ``MatchPlan.match(kp1, kp2, raw_results=True)`` up to the order of the rows.  Pure numpy.
+
+    :param idx, dist: the two ``(n1, k)`` int32 arrays of ``MatchPlan.knn``, ``k >= 2``
+    :param ratio: None (``par.MatchRatio``) or a number with ``ratio ** 2 <= 1``: above 1 the brute-force scan pairs a query
+                  without any candidate with index 0, which has no counterpart here
+    :return: ``(m, 2)`` int32, ascending in i
+    """
+    idx = numpy.asarray(idx)
+    dist = numpy.asarray(dist)
+    if idx.ndim != 2 or idx.shape != dist.shape or idx.shape[1] < 2:
+        raise ValueError("ratio_filter needs idx and dist of one shape (n1, k) with k >= 2, not %s and %s" % (idx.shape, dist.shape))
+    r = par.MatchRatio if ratio is None else ratio
+    th = numpy.float32(r * r)
+    if not th <= numpy.float32(1):
+        raise ValueError("ratio ** 2 must be <= 1, not %r" % (float(th),))
+    f1 = numpy.where(dist[:, 0] < 0, numpy.float32(1e12), dist[:, 0].astype(numpy.float32)).astype(numpy.float32)
+    f2 = numpy.where(dist[:, 1] < 0, numpy.float32(1e12), dist[:, 1].astype(numpy.float32)).astype(numpy.float32)
+    with numpy.errstate(all="ignore"):
+        keep = (f2 != 0) & (f1 / f2 < th)
+    i = numpy.nonzero(keep)[0]
+    return numpy.stack([i, idx[i, 0]], axis=1).astype(numpy.int32)
+
+
 class MatchPlan(object):
     """Plan to compare sets of SIFT keypoints and find common ones.
 
@@ -171,6 +198,31 @@ class MatchPlan(object):
         result = (mask.view(numpy.bool_), model if winner.value >= 0 else None, int(votes.value))
         return result + ((votes_all, models_all),) if return_votes else result
 
+    KNN_MAX = 8
+
+    def knn(self, kp1, kp2, k=2):
+        """The k nearest neighbours in ``kp2`` of every keypoint of ``kp1`` WITH their descriptor distances (extension; DESIGN.md
+        section 7 row 7).  Row i holds the k smallest ``(distance, index)`` over the whole second list in ascending order, the
+        smaller index first among equal distances; the distance is the int32 L1 distance over the 128 descriptor bytes.
+        Positions, the region of interest and ``par`` play no part, and the plan's ``kpsize`` is left alone.
+        ``ratio_filter(idx, dist, ratio)`` applies the reference's ratio test to the result.
+
+        :param kp1, kp2: numpy records, device tensors of 144-byte records or ``SiftPlan.device_records()``, as for ``match``
+        :param k: 1 .. 8
+        :return: ``(idx, dist)``, two int32 arrays of shape (n1, k); -1 in both where the second list has fewer than k keypoints
+        """
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        k = int(k)
+        cols = min(max(k, 0), self.KNN_MAX)
+        idx = numpy.empty((n1, cols), dtype=numpy.int32)
+        dist = numpy.empty((n1, cols), dtype=numpy.int32)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_knn(self._handle, p1, n1, dev1, p2, n2, dev2, k, idx.ctypes.data, dist.ctypes.data))
+            if self.profile:
+                self.events += self._stage_events(self.KNN_STAGE_LABELS)
+        return idx, dist
+
     def _records(self, kp):
         if isinstance(kp, numpy.ndarray):
             arr = numpy.ascontiguousarray(kp)
@@ -184,15 +236,16 @@ class MatchPlan(object):
         return ptr, is_dev, nbytes // 144, keep
 
     STAGE_LABELS = ("copy H->D KP_1", "copy H->D KP_2", "matching", "copy D->H match")
+    KNN_STAGE_LABELS = ("copy H->D KP_1", "copy H->D KP_2", "knn", "copy D->H knn")
 
-    def _stage_events(self):
+    def _stage_events(self, labels=STAGE_LABELS):
         """The reference's profiling events of one ``match`` call (match.py:226, 237, 261, 263) with the device time of each
         stage in place of the pyopencl event: ``evt.profile.end - evt.profile.start`` is nanoseconds, as there.  A stage that
         did not run (a device-resident list, no pair to copy back) has no entry -- the reference appends none either."""
         from .plan import StageEvent
         ms = (C.c_float * 4)()
         _lib.check(_lib.lib().siftmi_match_last_stage_ms(self._handle, ms))
-        return [(label, StageEvent(v)) for label, v in zip(self.STAGE_LABELS, ms) if v >= 0.0]
+        return [(label, StageEvent(v)) for label, v in zip(labels, ms) if v >= 0.0]
 
     def log_profile(self):
         """Print the recorded stage times (the reference's classes share this loop: alignment.py:363-375, plan.py:832-846)"""
