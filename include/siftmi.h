@@ -265,6 +265,18 @@ int siftmi_match_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n
 int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
                      const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k,
                      int32_t *idx_out, int32_t *dist_out);
+/* siftmi_match_knn with the descriptor distance of the caller's choice (tests/knn_l2_ref.py).
+ *   metric       SIFTMI_METRIC_L1: siftmi_match_knn, bit for bit (it is this entry with metric 0).
+ *                SIFTMI_METRIC_L2SQ: d(i, j) is the SQUARED Euclidean distance, the sum over the 128 descriptor bytes of
+ *                (a - b)^2 as integers, 0 .. 8 323 200 (= 128 * 255^2), as int32; no square root is taken.  Everything else --
+ *                the order of a row, the padding, the empty lists, the stage times, the errors -- is siftmi_match_knn's.  The ratio
+ *                test on these distances with ratio^2 is Lowe's test on Euclidean distances with the ratio itself.
+ * SIFTMI_EINVAL, nothing written, nothing launched: a metric other than the two constants, and siftmi_match_knn's. */
+#define SIFTMI_METRIC_L1 0
+#define SIFTMI_METRIC_L2SQ 1
+int siftmi_match_knn_metric(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                            const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k, int32_t metric,
+                            int32_t *idx_out, int32_t *dist_out);
 /* Consensus filter over the pairs of a match (no reference counterpart: the reference hands this to the third-party
  * feature.sift_orsa, sift-src/alignment.py:54-57, 260-264).  n_hyp affine maps are solved from pseudo-random triples of matches,
  * every match votes for every map that brings its list-1 position within `tol` pixels of its list-2 position, the map with most

@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libsiftmi.so")
 
 OK, EINVAL, ENOMEM, EDEVICE, ECAPACITY = 0, -1, -2, -3, -4
+METRIC_L1, METRIC_L2SQ = 0, 1
 
 DTYPE_CODES = {"float32": 0, "uint8": 1, "uint16": 2, "uint32": 3, "uint64": 4, "int32": 5, "int64": 6,
                "float64": 7, "rgb8": 8}
@@ -86,6 +87,8 @@ _SIGNATURES = {
                                       C.POINTER(C.c_int64)]),
     "siftmi_match_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p]),
+    "siftmi_match_knn_metric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p]),
     "siftmi_match_consensus": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),

@@ -1,5 +1,5 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scan that returns distances (k_knn.hpp) and the consensus filter over the pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean) and the consensus filter over the pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -8,6 +8,7 @@
 #include "k_match.hpp"
 #include "k_match_window.hpp"
 #include "k_knn.hpp"
+#include "k_knn_l2.hpp"
 #include "k_consensus.hpp"
 
 using namespace siftk;
@@ -56,7 +57,8 @@ struct siftmi_matcher {
     float4 *w_meta = nullptr;
     int *w_order = nullptr;
     int64_t cap_w_cells = 0, cap_w_work = 0, cap_w_desc = 0, cap_w_meta = 0, cap_w_order = 0;
-    // k nearest neighbours (siftmi_match_knn): the partitions' keys and the result (n1 * k indices, then n1 * k distances); grown on demand
+    // k nearest neighbours (siftmi_match_knn_metric): the partitions' keys (32-bit words: one per L1 key, two per squared-Euclidean key)
+    // and the result (n1 * k indices, then n1 * k distances); grown on demand
     uint32_t *knn_keys = nullptr;
     int32_t *knn_out = nullptr;
     int64_t cap_knn_keys = 0, cap_knn_out = 0;
@@ -384,7 +386,7 @@ int siftmi_match_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n
     return rc;
 }
 
-// k nearest neighbours with their distances (k_knn.hpp; the contract is DESIGN.md section 7 row 7).
+// k nearest neighbours with their distances (k_knn.hpp, k_knn_l2.hpp; the contract is DESIGN.md section 7 rows 7 and 8).
 namespace {
 // the decomposition of match_direction: query blocks x partitions of the list, about 2048 workgroups, a partition a whole number
 // of tiles and at most SIFT_MATCH_MAX_PART elements
@@ -421,13 +423,32 @@ void launch_knn_merge(hipStream_t st, int K, const uint32_t *keys, int nq, int n
     default: hipLaunchKernelGGL(knn_merge_kernel<8>, grid, dim3(256), 0, st, keys, nq, nparts, part_len, k, idx, dist); break;
     }
 }
+void launch_knn_l2_partial(hipStream_t st, int K, dim3 grid, const uint8_t *dq, int nq, const uint8_t *dl, int nl, int part_len, uint64_t *keys) {
+    switch (K) {
+    case 1: hipLaunchKernelGGL(knn_l2_partial_kernel<1>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    case 2: hipLaunchKernelGGL(knn_l2_partial_kernel<2>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    case 4: hipLaunchKernelGGL(knn_l2_partial_kernel<4>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    default: hipLaunchKernelGGL(knn_l2_partial_kernel<8>, grid, dim3(256), 0, st, dq, nq, dl, nl, part_len, keys); break;
+    }
+}
+void launch_knn_l2_merge(hipStream_t st, int K, const uint64_t *keys, const uint8_t *dq, int nq, int nparts, int k, int32_t *idx, int32_t *dist) {
+    const dim3 grid((unsigned)((nq + 255) / 256));
+    switch (K) {
+    case 1: hipLaunchKernelGGL(knn_l2_merge_kernel<1>, grid, dim3(256), 0, st, keys, dq, nq, nparts, k, idx, dist); break;
+    case 2: hipLaunchKernelGGL(knn_l2_merge_kernel<2>, grid, dim3(256), 0, st, keys, dq, nq, nparts, k, idx, dist); break;
+    case 4: hipLaunchKernelGGL(knn_l2_merge_kernel<4>, grid, dim3(256), 0, st, keys, dq, nq, nparts, k, idx, dist); break;
+    default: hipLaunchKernelGGL(knn_l2_merge_kernel<8>, grid, dim3(256), 0, st, keys, dq, nq, nparts, k, idx, dist); break;
+    }
+}
 }  // namespace
 
-int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
-                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k,
-                     int32_t *idx_out, int32_t *dist_out) {
+int siftmi_match_knn_metric(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                            const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k, int32_t metric,
+                            int32_t *idx_out, int32_t *dist_out) {
     if (!m) return fail(SIFTMI_EINVAL, "null argument");
     if (k < 1 || k > SIFT_KNN_MAX) return fail(SIFTMI_EINVAL, "k must be 1 .. %d, not %d", SIFT_KNN_MAX, k);
+    if (metric != SIFTMI_METRIC_L1 && metric != SIFTMI_METRIC_L2SQ)
+        return fail(SIFTMI_EINVAL, "metric must be SIFTMI_METRIC_L1 (0) or SIFTMI_METRIC_L2SQ (1), not %d", metric);
     if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
     if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
     if (n1 > 0 && (!idx_out || !dist_out)) return fail(SIFTMI_EINVAL, "null result buffer");
@@ -452,12 +473,18 @@ int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, 
     const int K = knn_instance(k);
     int qblocks, nparts, part_len;
     knn_partitions(n1, n2, &qblocks, &nparts, &part_len);
-    if ((rc = ensure((void **)&m->knn_keys, &m->cap_knn_keys, (int64_t)nparts * n1 * K, sizeof(uint32_t))) ||
+    const bool l2 = metric == SIFTMI_METRIC_L2SQ;
+    if ((rc = ensure((void **)&m->knn_keys, &m->cap_knn_keys, (int64_t)nparts * n1 * K * (l2 ? 2 : 1), sizeof(uint32_t))) ||
         (rc = ensure((void **)&m->knn_out, &m->cap_knn_out, 2 * (int64_t)cells, sizeof(int32_t)))) return rc;
     int32_t *d_idx = m->knn_out, *d_dist = m->knn_out + cells;
     hipEventRecord(m->ea, m->stream);
-    launch_knn_partial(m->stream, K, dim3((unsigned)qblocks, (unsigned)nparts), d1, (int)n1, d2, (int)n2, part_len, m->knn_keys);
-    launch_knn_merge(m->stream, K, m->knn_keys, (int)n1, nparts, part_len, k, d_idx, d_dist);
+    if (l2) {
+        launch_knn_l2_partial(m->stream, K, dim3((unsigned)qblocks, (unsigned)nparts), d1, (int)n1, d2, (int)n2, part_len, (uint64_t *)m->knn_keys);
+        launch_knn_l2_merge(m->stream, K, (const uint64_t *)m->knn_keys, d1, (int)n1, nparts, k, d_idx, d_dist);
+    } else {
+        launch_knn_partial(m->stream, K, dim3((unsigned)qblocks, (unsigned)nparts), d1, (int)n1, d2, (int)n2, part_len, m->knn_keys);
+        launch_knn_merge(m->stream, K, m->knn_keys, (int)n1, nparts, part_len, k, d_idx, d_dist);
+    }
     hipEventRecord(m->eb, m->stream);
     if (prof) hipEventRecord(m->ev[3], m->stream);
     HIPCHK(hipMemcpyAsync(idx_out, d_idx, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
@@ -473,6 +500,12 @@ int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, 
         hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
     }
     return SIFTMI_OK;
+}
+
+int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k,
+                     int32_t *idx_out, int32_t *dist_out) {
+    return siftmi_match_knn_metric(m, kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, k, SIFTMI_METRIC_L1, idx_out, dist_out);
 }
 
 // Consensus filter over the pairs of a match (k_consensus.hpp; the contract is DESIGN.md section 7 row 5).  The lists and the

@@ -23,7 +23,8 @@ def ratio_filter(idx, dist, ratio=None):
     """The reference's ratio test (matching_cpu.cl:103-108) on the result of ``MatchPlan.knn`` (extension), with a ratio of the
     caller's choice: the pairs ``(i, idx[i, 0])`` of the rows with ``dist2 != 0 and dist1 / dist2 < float32(ratio ** 2)`` in
     float32, where ``dist1, dist2 = dist[i, 0], dist[i, 1]`` and a missing distance (-1) counts as ``1e12f``.  With the default
-    ratio this is ``MatchPlan.match(kp1, kp2, raw_results=True)`` up to the order of the rows.  Pure numpy.
+    ratio this is ``MatchPlan.match(kp1, kp2, raw_results=True)`` up to the order of the rows.  On ``knn(..., metric="l2")``
+    results, whose distances are squared, it is Lowe's ratio test on Euclidean distances with ``ratio`` itself.  Pure numpy.
 
     :param idx, dist: the two ``(n1, k)`` int32 arrays of ``MatchPlan.knn``, ``k >= 2``
     :param ratio: None (``par.MatchRatio``) or a number with ``ratio ** 2 <= 1``: above 1 the brute-force scan pairs a query
@@ -200,17 +201,24 @@ class MatchPlan(object):
 
     KNN_MAX = 8
 
-    def knn(self, kp1, kp2, k=2):
+    KNN_METRICS = {"l1": _lib.METRIC_L1, "l2": _lib.METRIC_L2SQ}
+
+    def knn(self, kp1, kp2, k=2, metric="l1"):
         """The k nearest neighbours in ``kp2`` of every keypoint of ``kp1`` WITH their descriptor distances (extension; DESIGN.md
-        section 7 row 7).  Row i holds the k smallest ``(distance, index)`` over the whole second list in ascending order, the
-        smaller index first among equal distances; the distance is the int32 L1 distance over the 128 descriptor bytes.
-        Positions, the region of interest and ``par`` play no part, and the plan's ``kpsize`` is left alone.
-        ``ratio_filter(idx, dist, ratio)`` applies the reference's ratio test to the result.
+        section 7 rows 7 and 8).  Row i holds the k smallest ``(distance, index)`` over the whole second list in ascending order,
+        the smaller index first among equal distances.  The distance is an int32 over the 128 descriptor bytes: with
+        ``metric="l1"`` the L1 distance the reference's matcher uses (0 .. 32 640), with ``metric="l2"`` the SQUARED Euclidean
+        distance (0 .. 8 323 200; no square root is taken).  Positions, the region of interest and ``par`` play no part, and
+        the plan's ``kpsize`` is left alone.  ``ratio_filter(idx, dist, ratio)`` applies the reference's ratio test to the
+        result; on ``"l2"`` distances that is Lowe's test on Euclidean distances with ``ratio`` itself.
 
         :param kp1, kp2: numpy records, device tensors of 144-byte records or ``SiftPlan.device_records()``, as for ``match``
         :param k: 1 .. 8
+        :param metric: ``"l1"`` or ``"l2"``
         :return: ``(idx, dist)``, two int32 arrays of shape (n1, k); -1 in both where the second list has fewer than k keypoints
         """
+        if not isinstance(metric, str) or metric not in self.KNN_METRICS:
+            raise ValueError("metric must be 'l1' or 'l2', not %r" % (metric,))
         p1, dev1, n1, keep1 = self._records(kp1)
         p2, dev2, n2, keep2 = self._records(kp2)
         k = int(k)
@@ -218,7 +226,8 @@ class MatchPlan(object):
         idx = numpy.empty((n1, cols), dtype=numpy.int32)
         dist = numpy.empty((n1, cols), dtype=numpy.int32)
         with self._sem:
-            _lib.check(_lib.lib().siftmi_match_knn(self._handle, p1, n1, dev1, p2, n2, dev2, k, idx.ctypes.data, dist.ctypes.data))
+            _lib.check(_lib.lib().siftmi_match_knn_metric(self._handle, p1, n1, dev1, p2, n2, dev2, k, self.KNN_METRICS[metric],
+                                                          idx.ctypes.data, dist.ctypes.data))
             if self.profile:
                 self.events += self._stage_events(self.KNN_STAGE_LABELS)
         return idx, dist
