@@ -325,6 +325,15 @@ int siftmi_stage_blur(int32_t device_id, const float *in, float *out, int32_t W,
 int siftmi_stage_blur_ex(int32_t device_id, const void *in, int32_t in_dtype, float *out, int32_t W, int32_t H,
                          const float *taps, int32_t ntaps, int32_t norm, int32_t xcd_map, int32_t march_wgs,
                          int32_t *kernel_used);
+/* the f32, non-normalising blur with the fused octave hand-off (test hook: the launch a plan makes for plane 3 of an octave,
+ * which also writes out[2y][2x] to plane 0 of the next one, preprocess.cl:267-285).  xcd_map, march_wgs and *kernel_used as
+ * in siftmi_stage_blur_ex (bits 2-3 of xcd_map pick the small-plane form).  half: SIFTMI_STAGE_GUARD + (W/2)*(H/2) +
+ * SIFTMI_STAGE_GUARD floats; the device buffer is filled with 0xa5 bytes before the launch and returned whole, and the kernel
+ * is given the address behind the first guard: a sample no workgroup wrote, or a write outside the half plane, shows.  A tap
+ * count without a fused kernel runs the generic two-pass blur, which hands nothing off: `half` comes back as filled and
+ * *kernel_used is 0.  SIFTMI_EINVAL, nothing launched, for a null pointer, an empty plane or ntaps outside 1..64. */
+int siftmi_stage_blur_handoff(int32_t device_id, const float *in, float *out, float *half, int32_t W, int32_t H,
+                              const float *taps, int32_t ntaps, int32_t xcd_map, int32_t march_wgs, int32_t *kernel_used);
 int siftmi_stage_dog(int32_t device_id, const float *blur_a, const float *blur_b, float *out, int64_t n);
 /* blurs: 6 planes (H,W); out: (capacity,4) floats (peak,row,col,scale) for scales 1..3 */
 int siftmi_stage_local_maxmin(int32_t device_id, const float *blurs, int32_t W, int32_t H, int32_t octsize,

@@ -102,6 +102,8 @@ _SIGNATURES = {
     "siftmi_stage_blur": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     "siftmi_stage_blur_ex": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "siftmi_stage_blur_handoff": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "siftmi_stage_dog": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "siftmi_stage_local_maxmin": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params),
                                             C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),

@@ -2110,6 +2110,16 @@ bool desc_rows_fit(float sigma_oct, int32_t octsize) {
     return !((1.414f * spacing * 2.5f) + 0.5f >= (float)(SIFT_DESC_MAXRAD + 1));
 }
 
+// the launch choices the blur hooks expose (siftmi.h: siftmi_stage_blur_ex) on top of the defaults
+Options stage_blur_options(int32_t xcd_map, int32_t march_wgs) {
+    Options opt = g_default_options;
+    opt.xcd_map = (xcd_map & 1) ? 1 : 0;
+    opt.march_prio = (xcd_map & 2) ? 0 : 2;       // (forced where not off: the stage planes are smaller than the rule's)
+    opt.march_wgs = march_wgs > 0 ? march_wgs : 0;
+    if ((xcd_map >> 2) & 3) opt.small_blur = ((xcd_map >> 2) & 3) - 1;
+    return opt;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2169,11 +2179,7 @@ int siftmi_stage_blur_ex(int32_t dev, const void *in, int32_t in_dtype, float *o
     if ((rc = a.upload(in, N * esz)) || (rc = b.alloc(N * 4)) || (rc = t.alloc(N * 4)) || (rc = mm.alloc(8))) return rc;
     Taps tp;
     if ((rc = stage_taps(taps, ntaps, dt, tp))) return rc;
-    Options opt = g_default_options;
-    opt.xcd_map = (xcd_map & 1) ? 1 : 0;
-    opt.march_prio = (xcd_map & 2) ? 0 : 2;       // (forced where not off: the stage planes are smaller than the rule's)
-    opt.march_wgs = march_wgs > 0 ? march_wgs : 0;
-    if ((xcd_map >> 2) & 3) opt.small_blur = ((xcd_map >> 2) & 3) - 1;
+    const Options opt = stage_blur_options(xcd_map, march_wgs);
     uint32_t *mmp = mm.as<uint32_t>();
     if (norm) {
         hipLaunchKernelGGL(minmax_init, dim3(1), dim3(1), 0, 0, mmp);
@@ -2192,6 +2198,32 @@ int siftmi_stage_blur_ex(int32_t dev, const void *in, int32_t in_dtype, float *o
     if ((rc = stage_end())) return rc;
     if (kernel_used) *kernel_used = used;
     HIPCHK(hipMemcpy(out, b.p, N * 4, hipMemcpyDeviceToHost));
+    return SIFTMI_OK;
+}
+
+// The f32 blur stage with the fused octave hand-off: the launch a plan makes for plane 3 (launch_blur with `half` set), so that
+// a stage test reaches the hand-off line of every fused form at every tap count.  The half plane sits between two guards of
+// SIFTMI_STAGE_GUARD floats the kernel is not told of; the whole buffer is filled with 0xa5 bytes first and returned whole,
+// so a sample no workgroup wrote and a write before or beyond the half plane both show.
+int siftmi_stage_blur_handoff(int32_t dev, const float *in, float *out, float *half, int32_t W, int32_t H, const float *taps, int32_t ntaps,
+                              int32_t xcd_map, int32_t march_wgs, int32_t *kernel_used) {
+    int rc = stage_begin(dev); if (rc) return rc;
+    if (!in || !out || !half || !taps || W < 1 || H < 1) return fail(SIFTMI_EINVAL, "null argument or empty plane");
+    if (ntaps < 1 || ntaps > 64) return fail(SIFTMI_EINVAL, "ntaps must be in 1..64");
+    const size_t N = (size_t)W * H;
+    const size_t hslots = (size_t)SIFTMI_STAGE_GUARD + (size_t)(W / 2) * (H / 2) + SIFTMI_STAGE_GUARD;
+    DevBuf a, b, t, dt, h;
+    if ((rc = a.upload(in, N * 4)) || (rc = b.alloc(N * 4)) || (rc = t.alloc(N * 4)) || (rc = h.alloc(hslots * 4))) return rc;
+    HIPCHK(hipMemset(h.p, 0xa5, hslots * 4));
+    Taps tp;
+    if ((rc = stage_taps(taps, ntaps, dt, tp))) return rc;
+    const Options opt = stage_blur_options(xcd_map, march_wgs);
+    const BlurForm used = launch_blur_tiled<false>(opt, 0, a.as<float>(), b.as<float>(), W, H, tp, nullptr, h.as<float>() + SIFTMI_STAGE_GUARD);
+    if (used == BLUR_NONE) launch_blur_generic(0, a.as<float>(), b.as<float>(), t.as<float>(), W, H, tp, nullptr, false);     // (no hand-off: `half` stays as filled)
+    if ((rc = stage_end())) return rc;
+    if (kernel_used) *kernel_used = used;
+    HIPCHK(hipMemcpy(out, b.p, N * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(half, h.p, hslots * 4, hipMemcpyDeviceToHost));
     return SIFTMI_OK;
 }
 

@@ -112,7 +112,8 @@ def test_tile2_normalising_and_typed_instances(siftlib, oracle, shape):
 @pytest.mark.parametrize("shape", [(1024, 1024), (1023, 901)])
 def test_tile2_frames_and_fused_half(siftlib, oracle, shape):
     """Frames whose octave 0 takes blur_tile2_kernel under the default size rule: its plane-3 launch also writes the next
-    octave's plane 0 (`half`), which every later octave's keypoints depend on."""
+    octave's plane 0 (`half`), which every later octave's keypoints depend on.  (The hand-off as a stage, with guards around
+    the half plane and every tap count: tests/test_gpu_handoff.py.)"""
     import sift_pyocl_amd as sp
     img = smooth_noise(shape, seed=41, sigma=2.0)
     taps = oracle.gaussian_taps(17 / 8.0, 17)
