@@ -294,6 +294,31 @@ int siftmi_match_consensus(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_
                            const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
                            int32_t n_hyp, float tol, uint32_t seed, uint8_t *mask, float *model, int32_t *winner,
                            int32_t *winner_votes, int32_t *votes_all, float *models_all, double *kernel_ms);
+/* Least-squares affine map of the pairs of a match, entirely on the device (no reference counterpart: the reference's
+ * utils.matching_correction stops before the solve, sift-src/utils.py:156-189; the host form is utils.affine_least_squares).
+ * Pair j is gathered to f32 (x0, y0, x1, y1) as for the consensus filter and is *used* iff (mask == NULL || mask[j] != 0) and all
+ * four are finite (an index outside its list gives NaN); the used pairs are fitted in binary64 by centred normal equations: means,
+ * seven centred moments, a 2 x 2 solve, the sum of squared residuals of the f64 model.  Every sum is formed in one fixed order
+ * (256 lanes per workgroup, `blocks` workgroups, pair j on lane j mod 256 * blocks; lane sums in ascending j, a fixed tree over
+ * the lanes, the workgroups in ascending order), every operation rounded once: deterministic for (inputs, blocks) and restated
+ * exactly in numpy (tests/fit_ref.py).  Lists, pairs and mask are used where they lie; host ones
+ * are staged in the matcher's buffers.  One stream synchronisation and one 160-byte copy back per call.
+ * n_pairs == 0: EMPTY, nothing launched.  SIFTMI_EINVAL, nothing launched, nothing written: a null matcher or out, a negative
+ * count or one above 2^31 - 1, a null list or null pairs with a non-zero count, blocks outside 0..1024.
+ *   mask       optional, n_pairs bytes, non-zero = use the pair (a consensus mask)
+ *   blocks     workgroups of the three passes, 1..1024; 0: min(256, max(1, ceil(n_pairs / 256)))
+ *   out        host, 20 doubles, all written by every call that returns SIFTMI_OK:
+ *              [0] status: 0 OK, 1 EMPTY (no used pair: [1] is 0, the rest NaN), 2 DEGENERATE (n < 3 or
+ *                  !(fabs(det) > 1e-12 * fmax(1, Sxx*Syy)), the rule of utils.affine_least_squares: [13..19] NaN)
+ *              [1] n, the used pairs      [2..5] the means mx, my, mu, mv of x0, y0, x1, y1
+ *              [6..12] Sxx, Sxy, Syy, Sxu, Syu, Sxv, Syv, sums over the used pairs of products of the centred coordinates
+ *              [13..18] a, b, c, d, e, f: x' = a x + b y + c, y' = d x + e y + f (the order of siftmi_match_consensus)
+ *              [19] ssr, the sum of squared residuals; rms = sqrt(ssr / n)
+ *   kernel_ms  optional: hipEvent time from the gather to the last kernel */
+int siftmi_match_fit(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
+                     const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
+                     const uint8_t *mask, int32_t mask_is_device, int32_t blocks, double *out, double *kernel_ms);
 int siftmi_match_last_kernel_ms(const siftmi_matcher *plan, float *ms);
 /* profile != 0 at creation: device time in ms of the last call's stages, in the order of the events the reference
  * appends under profile=True (sift-src/match.py:226-263): ms4[0] "copy H->D KP_1", [1] "copy H->D KP_2", [2] "matching",

@@ -14,7 +14,9 @@ Behavioural notes (deliberate):
     the ``extra`` margin of its output undefined);
   * ``orsa=True`` needs the third-party ``feature`` module, exactly as in the reference; absent -> warning;
   * ``robust=True`` (extension, off by default) filters the matches with ``MatchPlan.consensus`` on the device before
-    the fit: the pairs that agree on one affine map within ``robust_tol`` pixels are kept, the rest never reach it.
+    the fit: the pairs that agree on one affine map within ``robust_tol`` pixels are kept, the rest never reach it;
+  * ``estimate="device"`` (extension, off by default) takes the affine map from ``MatchPlan.fit``: the same centred normal
+    equations, summed on the device over the lists where ``match()`` read them, without the host's gathers.
 """
 import ctypes as C
 import logging
@@ -224,7 +226,7 @@ class LinearAlign(object):
 
     # ------------------------------------------------------------------ public entry
     def align(self, img, shift_only=False, return_all=False, double_check=False, relative=False, orsa=False,
-              robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None):
+              robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None, estimate="host"):
         """Align `img` on the reference image.
 
         :param img: image to align (same shape as the reference)
@@ -244,8 +246,19 @@ class LinearAlign(object):
                        dense frames; everything after the match is unchanged.  When the true displacement exceeds ``max_shift``
                        the true partners are not candidates: expect few or wrong matches, not an error.  On sparse frames a
                        keypoint with a single candidate always pairs with it; ``robust=True`` is recommended there.
+        :param estimate: (extension) ``"host"`` (default): the affine map is fitted in numpy on the gathered positions.
+                       ``"device"``: it comes from ``MatchPlan.fit`` on the two lists where the matcher read them (with the
+                       consensus mask under ``robust``), and the matched positions are not gathered on the host at all.  Both
+                       solve the same centred normal equations in float64 and differ in the order of the sums only: matrix
+                       and offset agree to float32 rounding.  With ``return_all``, ``"rms"`` is then ``sqrt(ssr / n)`` of the
+                       float64 map as the device computed it, not the residual of the float32 matrix and offset that the host
+                       path reports.  The host path is taken all the same, with its exact results, under ``shift_only``,
+                       under ``double_check``, when ORSA filtered the matches, below 18 usable pairs and for degenerate
+                       (collinear) positions.
         :return: the aligned image, the dict, or None when no keypoint matches
         """
+        if estimate not in ("host", "device"):
+            raise ValueError("estimate must be 'host' or 'device', not %r" % (estimate,))
         logger.debug("ref_keypoints: %s" % self.ref_kp.size)
         data = numpy.ascontiguousarray(img, numpy.uint8 if self.RGB else numpy.float32)
         with self.sem:
@@ -264,10 +277,14 @@ class LinearAlign(object):
             ref_used = self.ref_kp
             # (the 16-byte heads are first packed into a dense (n, 4) array -- one strided pass -- and indexed there: a fancy
             # index straight into the 144-byte records took 13 ms for 2 x 195 k pairs, this takes 3)
-            if self._ref_heads is None:
-                self._ref_heads = numpy.ascontiguousarray(self._xysa(ref_used))
-            g0 = self._ref_heads[pairs[:, 0]]
-            g1 = numpy.ascontiguousarray(self._xysa(kp))[pairs[:, 1]]
+            def gathered():
+                if self._ref_heads is None:
+                    self._ref_heads = numpy.ascontiguousarray(self._xysa(ref_used))
+                return self._ref_heads[pairs[:, 0]], numpy.ascontiguousarray(self._xysa(kp))[pairs[:, 1]]
+
+            # estimate="device": the fit reads the lists in HBM and the gathers wait until something else needs them
+            on_device = estimate == "device" and not shift_only and not double_check and not (orsa and feature is not None)
+            g0, g1 = (None, None) if on_device else gathered()
 
             def matched_records():
                 both = numpy.recarray(shape=pairs.shape, dtype=MatchPlan.dtype_kp)
@@ -292,12 +309,26 @@ class LinearAlign(object):
                     found = self.match.consensus(ref_list, self.sift.device_records(), pairs, n_hyp=robust_hyp, tol=robust_tol, seed=0)
                 inliers = found[0]
                 if found[1] is None:
-                    logger.warning("No consensus among %s matches: all of them are used" % g0.shape[0])
-                else:
+                    logger.warning("No consensus among %s matches: all of them are used" % (n_pairs if on_device else g0.shape[0]))
+                elif not on_device:
                     g0, g1 = g0[inliers], g1[inliers]
                     n_pairs = g0.shape[0]
+            rms = None
+            if on_device:
+                voters = inliers if robust and found[1] is not None else None
+                model, rms, n_fit = self.match.fit(ref_list, self.sift.device_records(), pairs, mask=voters)
+                if model is None or n_fit < MIN_MATCHES_AFFINE:      # too few or degenerate: the host path, from its gathers on
+                    on_device, rms = False, None
+                    g0, g1 = gathered()
+                    if voters is not None:
+                        g0, g1 = g0[voters], g1[voters]
+                        n_pairs = g0.shape[0]
             enough = n_pairs >= MIN_MATCHES_AFFINE
-            if shift_only or not enough:
+            if on_device:
+                logger.debug("Common keypoints: %s" % n_fit)
+                a, b, c, d, e, f = model
+                matrix, offset = numpy.array([[e, d], [b, a]], dtype=numpy.float32), numpy.array([f, c], dtype=numpy.float32)
+            elif shift_only or not enough:
                 (logger.debug if shift_only else logger.warning)("Shift Only mode: Common keypoints: %s" % n_pairs)
                 matrix, offset = self._median_shift(g0, g1)
             else:
@@ -317,10 +348,11 @@ class LinearAlign(object):
             return result
         # residual of the fitted map on the matched keypoints, in pixels (alignment.py:349-351)
         # (written out instead of numpy.dot(matrix, src): a threaded BLAS has no business in a 2 x 2 product, see utils.py)
-        sy, sx = g0[:, 1], g0[:, 0]
-        ry = matrix[0, 0] * sy + matrix[0, 1] * sx + offset[0] - g1[:, 1]
-        rx = matrix[1, 0] * sy + matrix[1, 1] * sx + offset[1] - g1[:, 0]
-        rms = numpy.sqrt((ry * ry + rx * rx).mean())
+        if rms is None:
+            sy, sx = g0[:, 1], g0[:, 0]
+            ry = matrix[0, 0] * sy + matrix[0, 1] * sx + offset[0] - g1[:, 1]
+            rx = matrix[1, 0] * sy + matrix[1, 1] * sx + offset[1] - g1[:, 0]
+            rms = numpy.sqrt((ry * ry + rx * rx).mean())
         if matching is None:
             matching = matched_records()
         out = {"result": result, "keypoint": kp, "matching": matching, "offset": offset, "matrix": matrix, "rms": rms}

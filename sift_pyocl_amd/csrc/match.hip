@@ -1,5 +1,5 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean) and the consensus filter over the pairs (k_consensus.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean), the consensus filter over the pairs (k_consensus.hpp) and the least-squares affine map of the pairs (k_fit.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -10,6 +10,7 @@
 #include "k_knn.hpp"
 #include "k_knn_l2.hpp"
 #include "k_consensus.hpp"
+#include "k_fit.hpp"
 
 using namespace siftk;
 
@@ -62,6 +63,10 @@ struct siftmi_matcher {
     uint32_t *knn_keys = nullptr;
     int32_t *knn_out = nullptr;
     int64_t cap_knn_keys = 0, cap_knn_out = 0;
+    // least-squares fit (siftmi_match_fit): the staged copy of a host mask and the workgroups' partial sums; on demand
+    uint8_t *f_mask = nullptr;
+    int64_t cap_f_mask = 0;
+    FitPartials *f_part = nullptr;
 };
 
 namespace {
@@ -121,7 +126,7 @@ int siftmi_match_destroy(siftmi_matcher *m) {
     for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
                     (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result,
                     (void *)m->w_cells, (void *)m->w_work, (void *)m->w_desc, (void *)m->w_meta, (void *)m->w_order,
-                    (void *)m->knn_keys, (void *)m->knn_out})
+                    (void *)m->knn_keys, (void *)m->knn_out, (void *)m->f_mask, (void *)m->f_part})
         if (q) hipFree(q);
     if (m->ec_a) hipEventDestroy(m->ec_a);
     if (m->ec_b) hipEventDestroy(m->ec_b);
@@ -582,6 +587,63 @@ int siftmi_match_consensus(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_
     *winner = res.winner;
     if (winner_votes) *winner_votes = res.votes;
     if (res.winner >= 0 && model) memcpy(model, res.model, sizeof res.model);
+    return SIFTMI_OK;
+}
+
+// Least-squares affine map of the pairs of a match (k_fit.hpp; the contract is DESIGN.md section 7 row 9).  The lists, the pairs
+// and the mask are used where they lie; host ones are staged in the matcher's own buffers.
+int siftmi_match_fit(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                     const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
+                     const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
+                     const uint8_t *mask, int32_t mask_is_device, int32_t blocks, double *out, double *kernel_ms) {
+    if (!m || !out) return fail(SIFTMI_EINVAL, "null argument");
+    if (n1 < 0 || n2 < 0 || n_pairs < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff || n_pairs > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n_pairs > 0 && !pairs) return fail(SIFTMI_EINVAL, "null pairs with %lld pairs", (long long)n_pairs);
+    if (blocks < 0 || blocks > SIFT_FIT_MAX_BLOCKS) return fail(SIFTMI_EINVAL, "blocks %d outside 0..%d", blocks, SIFT_FIT_MAX_BLOCKS);
+    HIPCHK(hipSetDevice(m->device));
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (n_pairs == 0) {     // EMPTY, nothing is launched
+        for (int k = 0; k < SIFT_FIT_OUT; k++) out[k] = std::nan("");
+        out[SIFT_FIT_STATUS] = 1.0; out[SIFT_FIT_N] = 0.0;
+        return SIFTMI_OK;
+    }
+    if (kp1_is_device || kp2_is_device || pairs_is_device || (mask && mask_is_device)) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2, *dm = mask;
+    const int2 *dp = (const int2 *)pairs;
+    int rc;
+    if (!kp1_is_device && n1 > 0 && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (!kp2_is_device && n2 > 0 && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (!pairs_is_device) {
+        if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, n_pairs, sizeof(int2)))) return rc;
+        HIPCHK(hipMemcpyAsync(m->pairs, pairs, (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, m->stream));
+        dp = m->pairs;
+    }
+    if (mask && !mask_is_device) {
+        if ((rc = ensure((void **)&m->f_mask, &m->cap_f_mask, n_pairs, 1))) return rc;
+        HIPCHK(hipMemcpyAsync(m->f_mask, mask, (size_t)n_pairs, hipMemcpyHostToDevice, m->stream));
+        dm = m->f_mask;
+    }
+    if ((rc = ensure((void **)&m->c_pts, &m->cap_c_pts, n_pairs, sizeof(float4)))) return rc;
+    if (!m->f_part) HIPCHK(hipMalloc((void **)&m->f_part, sizeof(FitPartials)));
+    const int M = (int)n_pairs;
+    // the rule: a workgroup per 256 pairs up to 256 workgroups, one per CU; beyond that a lane owns several pairs
+    int B = blocks;
+    if (B == 0) { B = (M + SIFT_FIT_THREADS - 1) / SIFT_FIT_THREADS; if (B > 256) B = 256; if (B < 1) B = 1; }
+    const dim3 grid((unsigned)B), wg(SIFT_FIT_THREADS);
+    hipEventRecord(m->ec_a, m->stream);
+    hipLaunchKernelGGL(consensus_gather_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, m->stream, d1, (int)n1, d2, (int)n2, dp, M, m->c_pts);
+    hipLaunchKernelGGL(fit_pass1_kernel, grid, wg, 0, m->stream, (const float4 *)m->c_pts, dm, M, m->f_part);
+    hipLaunchKernelGGL(fit_pass2_kernel, grid, wg, 0, m->stream, (const float4 *)m->c_pts, dm, M, m->f_part);
+    hipLaunchKernelGGL(fit_pass3_kernel, grid, wg, 0, m->stream, (const float4 *)m->c_pts, dm, M, m->f_part);
+    hipLaunchKernelGGL(fit_finish_kernel, dim3(1), dim3(64), 0, m->stream, m->f_part, B);
+    hipEventRecord(m->ec_b, m->stream);
+    double res[SIFT_FIT_OUT];
+    HIPCHK(hipMemcpyAsync(res, m->f_part->out, sizeof res, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
+    memcpy(out, res, sizeof res);
     return SIFTMI_OK;
 }
 

@@ -199,6 +199,50 @@ class MatchPlan(object):
         result = (mask.view(numpy.bool_), model if winner.value >= 0 else None, int(votes.value))
         return result + ((votes_all, models_all),) if return_votes else result
 
+    FIT_OK, FIT_EMPTY, FIT_DEGENERATE = 0, 1, 2
+
+    def fit(self, kp1, kp2, pairs, mask=None, blocks=0, return_moments=False):
+        """Least-squares affine map that sends the ``kp1`` positions of the pairs onto their ``kp2`` positions, computed on the
+        device (extension; what ``utils.affine_least_squares`` computes on the host).  Centred normal equations in float64,
+        every sum formed in one fixed order: deterministic for given inputs and ``blocks`` (DESIGN.md section 7 row 9 is the
+        exact arithmetic).  A pair with an index outside its list or a non-finite coordinate is skipped.
+
+        :param kp1, kp2: the keypoint lists ``pairs`` indexes, numpy records or device tensors as for ``match``
+        :param pairs: (M, 2) int32 indices, a numpy array or a device tensor
+        :param mask: None, or (M,) bool / uint8, a numpy array or a device tensor: only the pairs with a non-zero entry are
+                     fitted (the mask of ``consensus``)
+        :param blocks: workgroups the sums are spread over, 1 .. 1024 (part of the summation order); 0 picks by M
+        :return: ``(model, rms, n)``: float64 (a, b, c, d, e, f) with x' = a x + b y + c, y' = d x + e y + f (the order of
+                 ``consensus``), the root mean square residual of that map over the fitted pairs in pixels, and their number.
+                 ``model`` is None and ``rms`` NaN when no pair is usable or the positions are degenerate (fewer than three,
+                 collinear).  With ``return_moments`` a fourth item: the 20 float64 values of ``siftmi_match_fit`` (status,
+                 n, four means, seven centred moments, the model, the sum of squared residuals).
+        """
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        pp, devp, pdtype, pshape, keepp = _pointer_of(pairs)
+        if pdtype != numpy.int32 or len(pshape) != 2 or pshape[1] != 2:
+            raise RuntimeError("pairs must be an (M, 2) int32 array")
+        n_pairs = int(pshape[0])
+        pm, devm, keepm = None, 0, None
+        if mask is not None:
+            if isinstance(mask, numpy.ndarray) and mask.dtype == numpy.bool_:
+                mask = mask.view(numpy.uint8)
+            pm, devm, mdtype, mshape, keepm = _pointer_of(mask)
+            if mdtype.itemsize != 1 or mdtype.kind not in "bu" or tuple(mshape) != (n_pairs,):
+                raise RuntimeError("mask must be an (M,) bool or uint8 array")
+        raw = numpy.empty(20, numpy.float64)
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_fit(self._handle, p1, n1, dev1, p2, n2, dev2, pp if n_pairs else None, n_pairs, devp,
+                                                   pm if n_pairs else None, devm, int(blocks), raw.ctypes.data, C.byref(ms)))
+            if self.profile:
+                from .plan import StageEvent
+                self.events.append(("fit", StageEvent(ms.value)))            # device time, gather to the last kernel
+        ok = raw[0] == self.FIT_OK
+        result = (raw[13:19].copy() if ok else None, float(numpy.sqrt(raw[19] / raw[1])) if ok else float("nan"), int(raw[1]))
+        return result + (raw,) if return_moments else result
+
     KNN_MAX = 8
 
     KNN_METRICS = {"l1": _lib.METRIC_L1, "l2": _lib.METRIC_L2SQ}
