@@ -277,6 +277,23 @@ int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, 
 int siftmi_match_knn_metric(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
                             const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k, int32_t metric,
                             int32_t *idx_out, int32_t *dist_out);
+/* siftmi_match_knn_metric over the CANDIDATES of a query only (extension; DESIGN.md section 7 row 10, restated in numpy by
+ * tests/knn_window_ref.py).  List-2 keypoint j is a candidate of list-1 keypoint i iff siftmi_match_window's predicate holds,
+ * fabsf((x2[j] - x1[i]) - sx) <= wx && fabsf((y2[j] - y1[i]) - sy) <= wy in f32, every operation rounded on its own (a NaN makes
+ * it false; wx / wy may be +inf).  Row i of the result holds the k smallest elements of {(d(i, j), j) : j a candidate of i} in
+ * ascending lexicographic order of (distance, index), d being the distance of `metric`; where i has fewer than k candidates (none
+ * included) the remaining slots hold -1 / -1.  The order is total: the result does not depend on the binning of the lists, on
+ * the order inside a cell or on scheduling.  The ratio, the region of interest and the matcher's pair capacity (`size`) play no
+ * part and are left alone.  With an infinite window, a zero shift and finite coordinates the result is siftmi_match_knn_metric's;
+ * exchanging the lists and negating the shift ranks the candidates of every list-2 keypoint among list 1.
+ * Both lists are used where they lie (host lists are staged).  n1 == 0 writes nothing, n2 == 0 writes -1 everywhere; neither
+ * launches anything.  siftmi_match_last_kernel_ms reports all kernels of the call, the binning of the lists included, and
+ * siftmi_match_last_stage_ms the call's stages as for siftmi_match_knn.
+ * SIFTMI_EINVAL, nothing written, nothing launched: siftmi_match_knn_metric's (k, metric, counts, null pointers), a count above
+ * 2^28 - 1, a negative or NaN window, a shift that is not finite. */
+int siftmi_match_knn_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                            const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k, int32_t metric,
+                            float wx, float wy, float sx, float sy, int32_t *idx_out, int32_t *dist_out);
 /* Consensus filter over the pairs of a match (no reference counterpart: the reference hands this to the third-party
  * feature.sift_orsa, sift-src/alignment.py:54-57, 260-264).  n_hyp affine maps are solved from pseudo-random triples of matches,
  * every match votes for every map that brings its list-1 position within `tol` pixels of its list-2 position, the map with most

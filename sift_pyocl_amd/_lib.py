@@ -89,6 +89,8 @@ _SIGNATURES = {
                                    C.c_void_p]),
     "siftmi_match_knn_metric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p]),
+    "siftmi_match_knn_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "siftmi_match_consensus": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),

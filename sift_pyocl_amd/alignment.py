@@ -26,7 +26,7 @@ import threading
 import numpy
 
 from . import _lib
-from .match import MatchPlan
+from .match import MatchPlan, ratio_filter
 from .plan import SiftPlan, StageEvent
 from .utils import affine_least_squares, matching_correction  # noqa: F401  (matching_correction: reference API)
 
@@ -226,7 +226,7 @@ class LinearAlign(object):
 
     # ------------------------------------------------------------------ public entry
     def align(self, img, shift_only=False, return_all=False, double_check=False, relative=False, orsa=False,
-              robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None, estimate="host"):
+              robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None, estimate="host", match_metric="l1", match_ratio=None):
         """Align `img` on the reference image.
 
         :param img: image to align (same shape as the reference)
@@ -255,10 +255,19 @@ class LinearAlign(object):
                        path reports.  The host path is taken all the same, with its exact results, under ``shift_only``,
                        under ``double_check``, when ORSA filtered the matches, below 18 usable pairs and for degenerate
                        (collinear) positions.
+        :param match_metric: (extension) ``"l1"`` (default) or ``"l2"``, the descriptor distance of the matcher
+        :param match_ratio: (extension) None, or the ratio of the ratio test.  With ``match_metric="l1"`` and no ratio the pairs
+                       come from ``MatchPlan.match``, the reference's fixed rule, exactly as before.  Otherwise they are
+                       ``ratio_filter(*MatchPlan.knn_window(ref, kp, 2, metric=match_metric, window=max_shift), ratio=match_ratio)``:
+                       with ``"l2"`` and 0.8 that is Lowe's ratio test on Euclidean distances, inside the window when
+                       ``max_shift`` is given and over the whole list when it is not; None stands for ``par.MatchRatio``.
+                       Everything after the match is unchanged.
         :return: the aligned image, the dict, or None when no keypoint matches
         """
         if estimate not in ("host", "device"):
             raise ValueError("estimate must be 'host' or 'device', not %r" % (estimate,))
+        if match_metric not in ("l1", "l2"):
+            raise ValueError("match_metric must be 'l1' or 'l2', not %r" % (match_metric,))
         logger.debug("ref_keypoints: %s" % self.ref_kp.size)
         data = numpy.ascontiguousarray(img, numpy.uint8 if self.RGB else numpy.float32)
         with self.sem:
@@ -266,7 +275,11 @@ class LinearAlign(object):
             logger.debug("mod image keypoints: %s" % kp.size)
             # both lists are matched where they lie in HBM: the reference list uploaded once, the new one still in the plan
             ref_list = self.ref_kp if self._ref_dev is None else self._ref_dev
-            pairs = self.match.match(ref_list, self.sift.device_records() if kp.size else kp, raw_results=True, window=max_shift)
+            records = self.sift.device_records() if kp.size else kp
+            if match_metric == "l1" and match_ratio is None:
+                pairs = self.match.match(ref_list, records, raw_results=True, window=max_shift)
+            else:
+                pairs = ratio_filter(*self.match.knn_window(ref_list, records, 2, metric=match_metric, window=max_shift), ratio=match_ratio)
             n_pairs = pairs.shape[0]
             if n_pairs == 0:
                 logger.warning("No matching keypoints")

@@ -1,5 +1,5 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean), the consensus filter over the pairs (k_consensus.hpp) and the least-squares affine map of the pairs (k_fit.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) and the least-squares affine map of the pairs (k_fit.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -9,6 +9,7 @@
 #include "k_match_window.hpp"
 #include "k_knn.hpp"
 #include "k_knn_l2.hpp"
+#include "k_knn_window.hpp"
 #include "k_consensus.hpp"
 #include "k_fit.hpp"
 
@@ -294,14 +295,14 @@ int mw_ensure(siftmi_matcher *m, int64_t n1, int64_t n2, bool both) {
     return SIFTMI_OK;
 }
 
-// one direction of the windowed scan: `nq` queries against the candidates among `nl` list elements (the scratch is sized by
-// mw_ensure).  reverse: the queries are list-2 keypoints; the predicate keeps (x2 - x1) - sx, so their window centre is x2 - sx.
-int match_window_direction(siftmi_matcher *m, const uint8_t *dq, int64_t nq, const uint8_t *dl, int64_t nl, int reverse, float wx, float wy,
-                           float sx, float sy, float ratio_th, int2 *pairs, int cap, int *nearest) {
+// the grid of one scan: the extent of the list, both histograms, their scans with the work list, the dense cell-sorted copy of
+// the list and the queries' order (the scratch is sized by mw_ensure).  (cx, cy) is the shift of the queries' window centre.
+struct MwScratch { uint32_t *hdr; int *start_l, *start_q; int work_cap; };
+int mw_build_grid(siftmi_matcher *m, const uint8_t *dq, int64_t nq, const uint8_t *dl, int64_t nl, float wx, float wy, float cx, float cy,
+                  MwScratch *out) {
     uint32_t *hdr = (uint32_t *)m->w_cells;
     int *cnt_l = m->w_cells + SIFT_MW_HDR, *cnt_q = cnt_l + SIFT_MW_MAXCELLS + 1;
     int *start_l = cnt_q + SIFT_MW_MAXCELLS + 1, *start_q = start_l + SIFT_MW_MAXCELLS + 1;
-    const float cx = reverse ? -sx : sx, cy = reverse ? -sy : sy;
     const int work_cap = (int)mw_work_cap(nq);
     const dim3 bl((unsigned)((nl + 255) / 256)), bq((unsigned)((nq + 255) / 256));
     // minima start at 0xffffffff, maxima, the work count and both histograms at 0
@@ -314,8 +315,19 @@ int match_window_direction(siftmi_matcher *m, const uint8_t *dq, int64_t nq, con
     hipLaunchKernelGGL(mw_scatter_list_kernel, dim3((unsigned)((nl * 8 + 255) / 256)), dim3(256), 0, m->stream, dl, (int)nl,
                        (const uint32_t *)hdr, wx, wy, cnt_l, m->w_desc, m->w_meta);
     hipLaunchKernelGGL(mw_scatter_query_kernel, bq, dim3(256), 0, m->stream, dq, (int)nq, (const uint32_t *)hdr, wx, wy, cx, cy, cnt_q, m->w_order);
-    hipLaunchKernelGGL(mw_match_kernel, dim3((unsigned)work_cap), dim3(256), 0, m->stream, dq, (int)nq, (int)nl, (const uint32_t *)hdr,
-                       wx, wy, sx, sy, reverse, (const int *)start_l, (const int *)start_q, (const int *)m->w_order, (const int2 *)m->w_work,
+    *out = {hdr, start_l, start_q, work_cap};
+    return SIFTMI_OK;
+}
+
+// one direction of the windowed scan: `nq` queries against the candidates among `nl` list elements (the scratch is sized by
+// mw_ensure).  reverse: the queries are list-2 keypoints; the predicate keeps (x2 - x1) - sx, so their window centre is x2 - sx.
+int match_window_direction(siftmi_matcher *m, const uint8_t *dq, int64_t nq, const uint8_t *dl, int64_t nl, int reverse, float wx, float wy,
+                           float sx, float sy, float ratio_th, int2 *pairs, int cap, int *nearest) {
+    MwScratch s;
+    int rc;
+    if ((rc = mw_build_grid(m, dq, nq, dl, nl, wx, wy, reverse ? -sx : sx, reverse ? -sy : sy, &s))) return rc;
+    hipLaunchKernelGGL(mw_match_kernel, dim3((unsigned)s.work_cap), dim3(256), 0, m->stream, dq, (int)nq, (int)nl, (const uint32_t *)s.hdr,
+                       wx, wy, sx, sy, reverse, (const int *)s.start_l, (const int *)s.start_q, (const int *)m->w_order, (const int2 *)m->w_work,
                        (const uint4 *)m->w_desc, (const float4 *)m->w_meta, ratio_th, pairs, m->counter, cap, nearest);
     return SIFTMI_OK;
 }
@@ -511,6 +523,81 @@ int siftmi_match_knn(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, 
                      const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k,
                      int32_t *idx_out, int32_t *dist_out) {
     return siftmi_match_knn_metric(m, kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, k, SIFTMI_METRIC_L1, idx_out, dist_out);
+}
+
+// k nearest neighbours inside a search window (k_knn_window.hpp; the contract is DESIGN.md section 7 row 10)
+extern "C++" {
+namespace {
+template <bool L2>
+void launch_mw_knn(siftmi_matcher *m, int K, const MwScratch &s, const uint8_t *dq, int nq, int nl, float wx, float wy, float sx, float sy,
+                   int k, int32_t *idx, int32_t *dist) {
+    const dim3 grid((unsigned)s.work_cap);
+#define SIFT_MW_KNN_ARGS dq, nq, nl, (const uint32_t *)s.hdr, wx, wy, sx, sy, (const int *)s.start_l, (const int *)s.start_q, \
+                         (const int *)m->w_order, (const int2 *)m->w_work, (const uint4 *)m->w_desc, (const float4 *)m->w_meta, k, idx, dist
+    switch (K) {
+    case 1: hipLaunchKernelGGL((mw_knn_kernel<1, L2>), grid, dim3(256), 0, m->stream, SIFT_MW_KNN_ARGS); break;
+    case 2: hipLaunchKernelGGL((mw_knn_kernel<2, L2>), grid, dim3(256), 0, m->stream, SIFT_MW_KNN_ARGS); break;
+    case 4: hipLaunchKernelGGL((mw_knn_kernel<4, L2>), grid, dim3(256), 0, m->stream, SIFT_MW_KNN_ARGS); break;
+    default: hipLaunchKernelGGL((mw_knn_kernel<8, L2>), grid, dim3(256), 0, m->stream, SIFT_MW_KNN_ARGS); break;
+    }
+#undef SIFT_MW_KNN_ARGS
+}
+}  // namespace
+}  // extern "C++"
+
+int siftmi_match_knn_window(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                            const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t k, int32_t metric,
+                            float wx, float wy, float sx, float sy, int32_t *idx_out, int32_t *dist_out) {
+    if (!m) return fail(SIFTMI_EINVAL, "null argument");
+    if (k < 1 || k > SIFT_KNN_MAX) return fail(SIFTMI_EINVAL, "k must be 1 .. %d, not %d", SIFT_KNN_MAX, k);
+    if (metric != SIFTMI_METRIC_L1 && metric != SIFTMI_METRIC_L2SQ)
+        return fail(SIFTMI_EINVAL, "metric must be SIFTMI_METRIC_L1 (0) or SIFTMI_METRIC_L2SQ (1), not %d", metric);
+    if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff / 8 || n2 > 0x7fffffff / 8) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n1 > 0 && (!idx_out || !dist_out)) return fail(SIFTMI_EINVAL, "null result buffer");
+    if (!(wx >= 0.f) || !(wy >= 0.f)) return fail(SIFTMI_EINVAL, "the window must be >= 0 (it may be infinite), not (%g, %g)", wx, wy);
+    if (!std::isfinite(sx) || !std::isfinite(sy)) return fail(SIFTMI_EINVAL, "the window shift must be finite, not (%g, %g)", sx, sy);
+    HIPCHK(hipSetDevice(m->device));
+    for (float &v : m->stage_ms) v = -1.f;
+    m->last_ms = 0;
+    if (n1 == 0) return SIFTMI_OK;
+    const size_t cells = (size_t)n1 * (size_t)k;
+    if (n2 == 0) {                              // no candidate at all: nothing is launched
+        for (size_t t = 0; t < cells; t++) { idx_out[t] = -1; dist_out[t] = -1; }
+        return SIFTMI_OK;
+    }
+    if (kp1_is_device || kp2_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    int rc;
+    const bool prof = m->profile && m->ev[0];
+    if (prof) hipEventRecord(m->ev[0], m->stream);
+    if (!kp1_is_device && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (prof) hipEventRecord(m->ev[1], m->stream);
+    if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (prof) hipEventRecord(m->ev[2], m->stream);
+    if ((rc = mw_ensure(m, n1, n2, false)) ||
+        (rc = ensure((void **)&m->knn_out, &m->cap_knn_out, 2 * (int64_t)cells, sizeof(int32_t)))) return rc;
+    int32_t *d_idx = m->knn_out, *d_dist = m->knn_out + cells;
+    hipEventRecord(m->ea, m->stream);
+    MwScratch s;
+    if ((rc = mw_build_grid(m, d1, n1, d2, n2, wx, wy, sx, sy, &s))) return rc;
+    if (metric == SIFTMI_METRIC_L2SQ) launch_mw_knn<true>(m, knn_instance(k), s, d1, (int)n1, (int)n2, wx, wy, sx, sy, k, d_idx, d_dist);
+    else launch_mw_knn<false>(m, knn_instance(k), s, d1, (int)n1, (int)n2, wx, wy, sx, sy, k, d_idx, d_dist);
+    hipEventRecord(m->eb, m->stream);
+    if (prof) hipEventRecord(m->ev[3], m->stream);
+    HIPCHK(hipMemcpyAsync(idx_out, d_idx, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(dist_out, d_dist, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    if (prof) hipEventRecord(m->ev[4], m->stream);
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    hipEventElapsedTime(&m->last_ms, m->ea, m->eb);
+    if (prof) {
+        m->stage_ms[2] = m->last_ms;
+        if (!kp1_is_device) hipEventElapsedTime(&m->stage_ms[0], m->ev[0], m->ev[1]);
+        if (!kp2_is_device) hipEventElapsedTime(&m->stage_ms[1], m->ev[1], m->ev[2]);
+        hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
+    }
+    return SIFTMI_OK;
 }
 
 // Consensus filter over the pairs of a match (k_consensus.hpp; the contract is DESIGN.md section 7 row 5).  The lists and the

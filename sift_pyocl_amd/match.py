@@ -276,6 +276,53 @@ class MatchPlan(object):
                 self.events += self._stage_events(self.KNN_STAGE_LABELS)
         return idx, dist
 
+    def knn_window(self, kp1, kp2, k=2, metric="l1", window=None, window_shift=(0.0, 0.0)):
+        """``knn`` over the *candidates* of a keypoint only (extension): keypoint j of ``kp2`` is a
+        candidate of keypoint i of ``kp1`` iff ``abs((x2[j] - x1[i]) - sx) <= wx and abs((y2[j] - y1[i]) - sy) <= wy`` in float32,
+        every operation rounded on its own (``match(window=)``'s predicate; a NaN makes it false).  Row i holds the k smallest
+        ``(distance, index)`` over the candidates of i in ascending order, the smaller index first among equal distances; the
+        remaining slots of a row with fewer than k candidates -- none included -- hold -1 in both arrays.  The distance is
+        ``knn``'s, on either metric.  The lists are binned on a grid of window-sized cells, so a query costs the descriptors of
+        its neighbourhood instead of the whole list; the result does not depend on the grid.  ``par``, the region of interest and
+        the plan's ``kpsize`` play no part.  ``window=None`` is ``knn(kp1, kp2, k, metric)`` itself, the same call.  (The keywords
+        live in a method of their own because ``knn``'s parameter list is pinned by the tests of rows 7 and 8.)
+
+        Two identities: (W1) ``ratio_filter(*knn_window(a, b, 2, window=w, window_shift=s))`` is
+        ``match(a, b, raw_results=True, window=w, window_shift=s)`` as sorted rows -- a lone candidate always pairs, a query without
+        candidates never does; (W3) candidacy is symmetric under an exchange of the lists with the shift negated, so
+        ``knn_window(b, a, k, window=w, window_shift=(-sx, -sy))`` ranks the candidates of every ``kp2`` keypoint among ``kp1``.
+        ``window=inf`` with a zero shift and finite coordinates gives the rows of ``knn``.
+
+        :param kp1, kp2: numpy records, device tensors of 144-byte records or ``SiftPlan.device_records()``, as for ``match``
+        :param k: 1 .. 8
+        :param metric: ``"l1"`` or ``"l2"``
+        :param window: None (the whole list), or the half width of the search window in pixels, a scalar or an ``(wx, wy)`` pair
+                       (``inf`` is allowed; negative or NaN is an error)
+        :param window_shift: ``(sx, sy)``, the expected displacement of the second list against the first (finite); needs ``window``
+        :return: ``(idx, dist)``, two int32 arrays of shape (n1, k); -1 in both where a keypoint has fewer than k candidates
+        """
+        if window is None:
+            if tuple(window_shift) != (0.0, 0.0):
+                raise ValueError("window_shift=%r needs a window" % (window_shift,))
+            return self.knn(kp1, kp2, k, metric)
+        if not isinstance(metric, str) or metric not in self.KNN_METRICS:
+            raise ValueError("metric must be 'l1' or 'l2', not %r" % (metric,))
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        k = int(k)
+        cols = min(max(k, 0), self.KNN_MAX)
+        idx = numpy.empty((n1, cols), dtype=numpy.int32)
+        dist = numpy.empty((n1, cols), dtype=numpy.int32)
+        wx, wy = (window if hasattr(window, "__len__") else (window, window))
+        sx, sy = window_shift
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_knn_window(self._handle, p1, n1, dev1, p2, n2, dev2, k, self.KNN_METRICS[metric],
+                                                          C.c_float(wx), C.c_float(wy), C.c_float(sx), C.c_float(sy),
+                                                          idx.ctypes.data, dist.ctypes.data))
+            if self.profile:
+                self.events += self._stage_events(self.KNN_STAGE_LABELS)
+        return idx, dist
+
     def _records(self, kp):
         if isinstance(kp, numpy.ndarray):
             arr = numpy.ascontiguousarray(kp)
