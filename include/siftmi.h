@@ -142,7 +142,9 @@ int siftmi_plan_records_device(const siftmi_plan *plan, const siftmi_keypoint **
  * kernels (openCL/transform.cl:22, :116) as LinearAlign.align launches them (sift-src/alignment.py:325-348).
  *   out[y][x] = bilinear(image, (ty, tx)),  ty = matrix[0]*y + matrix[1]*x + offset[0],
  *                                           tx = matrix[2]*y + matrix[3]*x + offset[1]
- * with `fill` outside the image, for taps right of / below it, and where tx >= W-0.5 or ty >= H-0.5.
+ * with `fill` outside the image, for taps right of / below it, and where tx >= W-0.5 or ty >= H-0.5.  For RGB8 every
+ * channel is converted with (uint8_t): `fill` must lie in [0, 255], a value outside converts a float that uint8_t cannot hold,
+ * which C leaves undefined.
  *   image        H x W float32 (channels 1) or H x W x 3 uint8 (channels 3); NULL = the host image most recently
  *                handed to siftmi_plan_keypoints, still staged on the device (the reference's buffers["input"])
  *   out          OH x OW (x3) of the same element type; the whole output is written (the reference only

@@ -1906,14 +1906,14 @@ int siftmi_plan_transform(siftmi_plan *p, const void *image, int32_t image_is_de
     const size_t px = channels == 1 ? 4 : 3;
     const size_t in_bytes = (size_t)p->W * p->H * px, out_bytes = (size_t)OW * OH * px;
     const void *src = image;
+    // a device pointer on either side: ordered after what the NULL stream was given for it (siftmi.h, conventions)
+    if ((image && image_is_device) || out_is_device) HIPCHK(hipDeviceSynchronize());
     if (!image) {
         const int want = channels == 1 ? SIFTMI_F32 : SIFTMI_RGB8;
         if (p->raw_dtype != want)
             return fail(SIFTMI_EINVAL, "no staged input of the requested format (staged dtype %d, wanted %d)", p->raw_dtype, want);
         src = p->raw;
-    } else if (image_is_device) {
-        HIPCHK(hipDeviceSynchronize());
-    } else {
+    } else if (!image_is_device) {
         if (p->warp_in_bytes < in_bytes) {
             if (p->warp_in) hipFree(p->warp_in);
             p->warp_in = nullptr; p->warp_in_bytes = 0;
