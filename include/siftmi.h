@@ -138,6 +138,25 @@ int siftmi_plan_fetch(siftmi_plan *plan, siftmi_keypoint *out, int32_t out_is_de
 /* device address and count of the records of the last call; valid until the next siftmi_plan_keypoints on this plan
  * (lets MatchPlan consume them in place, as the reference matches pyopencl arrays: alignment.py:155-157,250) */
 int siftmi_plan_records_device(const siftmi_plan *plan, const siftmi_keypoint **records, int64_t *count);
+/* What the last finished siftmi_plan_keypoints left behind besides its records (read-only test hooks: the pyramid of every
+ * producer -- marching, tile and generic blurs, the fused hand-off, octave_tail_kernel -- compared plane by plane at plan level).
+ * The reference keeps the same planes in buffers["scale_<octave>_<scale>"] (plan.py:276-285) and reads its keypoint counter back
+ * after every local_maxmin (plan.py:642).  Neither call launches anything; both are valid until the next call on the plan.
+ * siftmi_plan_planes       copies the six blur planes of `octave` (scale 0 first, row pitch W) to the host buffer `out` of
+ *                          `capacity` floats, 6 * W * H of them, and returns the octave's W and H (either may be null).  It waits
+ *                          for the plan's streams only.  Octave planes are never rewritten within a call.
+ * siftmi_plan_last_counts  host integers of the complete read-back of the counters that the wait selected:
+ *   tail_first     first octave that octave_tail_kernel took in the run that produced the result, n_octaves of the plan when
+ *                  there was no tail launch (also after a tail time-out: the result then comes from the re-run)
+ *   candidates     [n_octaves] entries the octave's detection appended to its candidate list (a split octave 0's second slot
+ *                  folded in).  The fused detect-and-refine launch keeps no candidate list: its octaves read 0 here.
+ *   c_scale        [n_octaves][3] candidates of the octave per detection scale 1, 2, 3, as the refinement read them
+ *   n_octaves      octaves the two arrays have room for (>= the plan's)
+ * SIFTMI_EINVAL, nothing written: a null plan or buffer, a buffer that is too small, an octave outside 0..n_octaves-1, a plan
+ * that has not finished a call (none yet, or the last one failed). */
+int siftmi_plan_planes(siftmi_plan *plan, int32_t octave, float *out, int64_t capacity, int32_t *width, int32_t *height);
+int siftmi_plan_last_counts(const siftmi_plan *plan, int32_t *tail_first, int32_t *candidates, int32_t *c_scale,
+                            int32_t n_octaves);
 /* Affine warp with bilinear interpolation of an image of the plan's shape -- the `transform` / `transform_RGB`
  * kernels (openCL/transform.cl:22, :116) as LinearAlign.align launches them (sift-src/alignment.py:325-348).
  *   out[y][x] = bilinear(image, (ty, tx)),  ty = matrix[0]*y + matrix[1]*x + offset[0],

@@ -246,6 +246,11 @@ struct siftmi_plan {
     float last_min = 0, last_max = 0;
     int64_t last_count = 0;
     int last_overflow = 0;
+    // host integers of the last finished call (siftmi_plan_last_counts), copied from the complete read-back of its counters
+    bool last_valid = false;                  // a call has finished and none has been enqueued or failed since
+    int last_tail_first = 0;                  // tail_first_cur of the run that produced the result
+    int last_n_cand[SIFT_MAX_OCTAVES] = {0};
+    int last_c_scale[SIFT_MAX_OCTAVES][3] = {{0}};
     std::vector<void *> allocs;
 
     template <class T> int alloc(T **p, size_t nbytes) {
@@ -1134,6 +1139,7 @@ int plan_enqueue(siftmi_plan *p, const void *image, int32_t image_dtype, int32_t
     // (the two blocks alternate only if an image never overlaps its predecessor on the same plan: plan_wait -- or a drain
     // on an error path -- always comes between two enqueues; `in_flight` enforces it)
     if (p->in_flight) return fail(SIFTMI_EINVAL, "the plan still has an image in flight");
+    p->last_valid = false;       // the planes and counts of the previous call are about to be overwritten
     p->cnt = p->cnt_pair + p->cnt_parity;
     p->mm = p->cnt->mm;
     Counters *next_cnt = p->cnt_pair + (p->cnt_parity ^ 1);
@@ -1497,6 +1503,12 @@ int plan_wait(siftmi_plan *p, int64_t *n_out, int32_t *overflow) {
     }
     p->last_count = n;
     p->last_overflow = ovf;
+    p->last_tail_first = p->tail_first_cur;
+    for (int o = 0; o < SIFT_MAX_OCTAVES; o++) {
+        p->last_n_cand[o] = hc.n_cand[o] + (o == 0 ? hc.n_cand[SIFT_MAX_OCTAVES] : 0);   // (the slot of a split octave 0 belongs to octave 0)
+        for (int s = 0; s < 3; s++) p->last_c_scale[o][s] = hc.c_scale[o][s];
+    }
+    p->last_valid = true;
     p->last_group0 = (int)std::min<int64_t>(hc.g_out[0], n);
     p->last_group1 = (int)n - p->last_group0;
     *n_out = n;
@@ -1574,6 +1586,40 @@ int siftmi_plan_fetch(siftmi_plan *p, siftmi_keypoint *out, int32_t out_is_devic
     HIPCHK(hipMemcpyAsync(out, p->records + first, (size_t)count * sizeof(KpRecord),
                           out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
+    return SIFTMI_OK;
+}
+
+// The six blur planes of one octave as the last finished call left them (see include/siftmi.h).  Nothing is launched: the
+// plan's streams are waited for (they are idle after plan_wait) and the planes are copied out.
+int siftmi_plan_planes(siftmi_plan *p, int32_t octave, float *out, int64_t capacity, int32_t *width, int32_t *height) {
+    if (!p) return fail(SIFTMI_EINVAL, "null plan");
+    if (!out) return fail(SIFTMI_EINVAL, "null output buffer");
+    if (octave < 0 || octave >= p->n_oct) return fail(SIFTMI_EINVAL, "octave %d outside 0..%d", octave, p->n_oct - 1);
+    if (!p->last_valid || p->in_flight) return fail(SIFTMI_EINVAL, "the plan has not finished a call: there are no planes to read");
+    const int W = p->ow[(size_t)octave], H = p->oh[(size_t)octave];
+    const int64_t need = 6 * (int64_t)W * H;
+    if (capacity < need) return fail(SIFTMI_EINVAL, "buffer of %lld floats, octave %d needs 6 * %d * %d", (long long)capacity, octave, W, H);
+    HIPCHK(hipSetDevice(p->device));
+    for (hipStream_t s : {p->stream2, p->stream3})
+        if (s) HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(out, p->plane(octave, 0), (size_t)need * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (width) *width = W;
+    if (height) *height = H;
+    return SIFTMI_OK;
+}
+
+int siftmi_plan_last_counts(const siftmi_plan *p, int32_t *tail_first, int32_t *candidates, int32_t *c_scale, int32_t n_octaves) {
+    if (!p) return fail(SIFTMI_EINVAL, "null plan");
+    if (!tail_first || !candidates || !c_scale) return fail(SIFTMI_EINVAL, "null output");
+    if (n_octaves < p->n_oct) return fail(SIFTMI_EINVAL, "room for %d octaves, the plan has %d", n_octaves, p->n_oct);
+    if (!p->last_valid || p->in_flight) return fail(SIFTMI_EINVAL, "the plan has not finished a call: there are no counts to read");
+    *tail_first = p->last_tail_first;
+    for (int o = 0; o < p->n_oct; o++) {
+        const bool held = o < SIFT_MAX_OCTAVES;       // (Counters holds SIFT_MAX_OCTAVES octaves; a frame never has more)
+        candidates[o] = held ? p->last_n_cand[o] : 0;
+        for (int s = 0; s < 3; s++) c_scale[3 * o + s] = held ? p->last_c_scale[o][s] : 0;
+    }
     return SIFTMI_OK;
 }
 

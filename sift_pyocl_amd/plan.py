@@ -385,6 +385,36 @@ class SiftPlan(object):
         _lib.check(_lib.lib().siftmi_plan_records_device(self._handle, C.byref(ptr), C.byref(n)))
         return _DeviceRecords(ptr.value or 0, int(n.value), self)
 
+    def planes(self, octave):
+        """The six blur planes of `octave` as the last finished keypoints() call left them on the device: (6, H, W) float32,
+        scale 0 first (the reference's buffers["scale_<octave>_<scale>"]).  Nothing is launched; valid until the next call."""
+        octave = int(octave)
+        if not 0 <= octave < self.octave_max:
+            raise RuntimeError("octave %d outside 0..%d" % (octave, self.octave_max - 1))
+        w, h = (int(v) for v in self.scales[octave])
+        out = numpy.empty((6, h, w), numpy.float32)
+        gw, gh = C.c_int32(), C.c_int32()
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_plan_planes(self._handle, octave, out.ctypes.data, out.size, C.byref(gw), C.byref(gh)))
+        assert (gw.value, gh.value) == (w, h)
+        return out
+
+    def last_counts(self):
+        """Host integers of the last finished keypoints() call: dict(tail_first = first octave the one-launch form of the
+        small octaves took in the run that produced the result (the number of octaves: none), candidates = entries every
+        octave's detection appended to its candidate list (0 where detection and refinement are one launch, which keeps no
+        list), c_scale = (octaves, 3) candidates per detection scale 1, 2, 3 as the refinement read them)."""
+        n_oct = C.c_int32()
+        L = _lib.lib()
+        _lib.check(L.siftmi_plan_info(self._handle, C.byref(n_oct), None, None))
+        n = max(1, n_oct.value)
+        cand = numpy.zeros(n, numpy.int32)
+        cs = numpy.zeros((n, 3), numpy.int32)
+        first = C.c_int32()
+        with self._sem:
+            _lib.check(L.siftmi_plan_last_counts(self._handle, C.byref(first), cand.ctypes.data, cs.ctypes.data, n))
+        return dict(tail_first=int(first.value), candidates=[int(v) for v in cand[:n_oct.value]], c_scale=cs[:n_oct.value].copy())
+
     def minmax(self):
         """(min, max) of the last processed image (buffers["min"], buffers["max"] in the reference)."""
         mn, mx = C.c_float(), C.c_float()

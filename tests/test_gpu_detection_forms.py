@@ -14,7 +14,9 @@ tests/test_oracle_vs_ref.py::test_detection_on_crafted_planes_identical ties to 
 families.  There is no tolerance in this module: rows are sorted and compared as uint32.
 
 octave_tail_kernel's use of extrema_strip (its own buffer size, `pending` carried across strips) is not reached from here:
-its planes are produced inside the launch.  It stays covered end to end only."""
+its planes are produced inside the launch.  tests/test_gpu_pyramid_cases.py compares the planes and the candidate counts of the
+tail per octave at plan level, on frames where waves carry `pending` from strip to strip; the flush at a full buffer
+(pending > SIFT_TAIL_EXT_BUF) stays unreached: no frame parks more than 5 of its 32 slots (tests/test_pyramid_cases_host.py)."""
 import ctypes as C
 
 import numpy as np
