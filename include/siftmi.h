@@ -357,6 +357,28 @@ int siftmi_match_fit(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, 
                      const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
                      const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
                      const uint8_t *mask, int32_t mask_is_device, int32_t blocks, double *out, double *kernel_ms);
+/* Exact median displacement of the pairs of a match, entirely on the device: the translation-only estimate the reference takes with
+ * numpy.median on the host (sift-src/alignment.py:268-271).  Pair j is gathered and *used* as for siftmi_match_fit; its
+ * displacement is dx = x1 - x0, dy = y1 - y0 in f32 (+-inf from an overflow takes part).  Per axis, with n used pairs, lo and hi are
+ * the values of rank (n - 1) >> 1 and n >> 1 in the total order of f32 (-inf first, -0.0 < +0.0), found by a radix select with
+ * integer counters only, and the median is lo for odd n and (lo + hi) * 0.5f for even n: numpy.median's value, bit for bit up to
+ * the sign of a zero, for every grid (tests/shift_ref.py restates it in numpy).  Lists, pairs and mask
+ * are used where they lie; host ones are staged in the matcher's buffers.  One stream synchronisation per call.
+ * n_pairs == 0: EMPTY, nothing launched.  SIFTMI_EINVAL, nothing launched, nothing written: a null matcher, out or counts, a
+ * negative count or one above 2^31 - 1, a null list or null pairs with a non-zero count, blocks outside 0..1024, and with a
+ * keep mask a tol that is NaN or negative.
+ *   mask       optional, n_pairs bytes, non-zero = use the pair (a consensus mask)
+ *   blocks     workgroups of the kernels that walk the pairs, 1..1024; 0: siftmi_match_fit's rule.  The result does not depend on it
+ *   tol, keep  keep: optional, host, n_pairs bytes: keep[j] = 1 iff pair j is used, both medians are finite and
+ *              fabsf(dx - mdx) <= tol && fabsf(dy - mdy) <= tol in f32 (tol may be +inf), else 0; tol is ignored without keep
+ *   out        host, 6 floats: mdx, mdy, lo_dx, hi_dx, lo_dy, hi_dy; all NaN when no pair is used (EMPTY)
+ *   counts     host, 2: n, the used pairs, and n_keep, the kept pairs (0 without keep)
+ *   kernel_ms  optional: hipEvent time from the gather to the last kernel */
+int siftmi_match_shift(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                       const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
+                       const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
+                       const uint8_t *mask, int32_t mask_is_device, int32_t blocks,
+                       float tol, uint8_t *keep, float *out, int64_t *counts, double *kernel_ms);
 int siftmi_match_last_kernel_ms(const siftmi_matcher *plan, float *ms);
 /* profile != 0 at creation: device time in ms of the last call's stages, in the order of the events the reference
  * appends under profile=True (sift-src/match.py:226-263): ms4[0] "copy H->D KP_1", [1] "copy H->D KP_2", [2] "matching",

@@ -16,7 +16,9 @@ Behavioural notes (deliberate):
   * ``robust=True`` (extension, off by default) filters the matches with ``MatchPlan.consensus`` on the device before
     the fit: the pairs that agree on one affine map within ``robust_tol`` pixels are kept, the rest never reach it;
   * ``estimate="device"`` (extension, off by default) takes the affine map from ``MatchPlan.fit``: the same centred normal
-    equations, summed on the device over the lists where ``match()`` read them, without the host's gathers.
+    equations, summed on the device over the lists where ``match()`` read them, without the host's gathers;
+  * ``median="device"`` (extension, off by default) takes every translation-only estimate from ``MatchPlan.shift``: the
+    exact median displacement, selected on the device over the same lists, without the host's gathers.
 """
 import ctypes as C
 import logging
@@ -226,7 +228,8 @@ class LinearAlign(object):
 
     # ------------------------------------------------------------------ public entry
     def align(self, img, shift_only=False, return_all=False, double_check=False, relative=False, orsa=False,
-              robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None, estimate="host", match_metric="l1", match_ratio=None):
+              robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None, estimate="host", match_metric="l1", match_ratio=None,
+              median="host"):
         """Align `img` on the reference image.
 
         :param img: image to align (same shape as the reference)
@@ -262,8 +265,16 @@ class LinearAlign(object):
                        with ``"l2"`` and 0.8 that is Lowe's ratio test on Euclidean distances, inside the window when
                        ``max_shift`` is given and over the whole list when it is not; None stands for ``par.MatchRatio``.
                        Everything after the match is unchanged.
+        :param median: (extension) ``"host"`` (default): a translation-only estimate (``shift_only``, fewer than 18 usable pairs)
+                       is ``numpy.median`` of the gathered displacements.  ``"device"``: it is ``MatchPlan.shift`` on the two
+                       lists where the matcher read them (with the consensus mask under ``robust``): the same median, value
+                       for value, and without ``return_all`` the matched positions are not gathered on the host at all.  The
+                       host path is taken all the same under ``double_check`` and when ORSA filtered the matches.
+                       ``estimate=`` keeps its meaning; ``shift_only`` with ``estimate="device"`` alone stays the host path.
         :return: the aligned image, the dict, or None when no keypoint matches
         """
+        if median not in ("host", "device"):
+            raise ValueError("median must be 'host' or 'device', not %r" % (median,))
         if estimate not in ("host", "device"):
             raise ValueError("estimate must be 'host' or 'device', not %r" % (estimate,))
         if match_metric not in ("l1", "l2"):
@@ -297,7 +308,9 @@ class LinearAlign(object):
 
             # estimate="device": the fit reads the lists in HBM and the gathers wait until something else needs them
             on_device = estimate == "device" and not shift_only and not double_check and not (orsa and feature is not None)
-            g0, g1 = (None, None) if on_device else gathered()
+            # median="device": so does the median, and the gathers wait until an affine fit on the host or return_all needs them
+            dev_median = median == "device" and not double_check and not (orsa and feature is not None)
+            g0, g1 = (None, None) if on_device or dev_median else gathered()
 
             def matched_records():
                 both = numpy.recarray(shape=pairs.shape, dtype=MatchPlan.dtype_kp)
@@ -322,19 +335,25 @@ class LinearAlign(object):
                     found = self.match.consensus(ref_list, self.sift.device_records(), pairs, n_hyp=robust_hyp, tol=robust_tol, seed=0)
                 inliers = found[0]
                 if found[1] is None:
-                    logger.warning("No consensus among %s matches: all of them are used" % (n_pairs if on_device else g0.shape[0]))
-                elif not on_device:
+                    logger.warning("No consensus among %s matches: all of them are used" % (n_pairs if g0 is None else g0.shape[0]))
+                elif g0 is not None:
                     g0, g1 = g0[inliers], g1[inliers]
                     n_pairs = g0.shape[0]
+            voters = inliers if robust and found[1] is not None else None      # what a device estimate takes as its mask
+
+            def gathered_voters():
+                a, b = gathered()
+                return (a, b) if voters is None else (a[voters], b[voters])
+
+            if dev_median and voters is not None:
+                n_pairs = int(voters.sum())
             rms = None
             if on_device:
-                voters = inliers if robust and found[1] is not None else None
                 model, rms, n_fit = self.match.fit(ref_list, self.sift.device_records(), pairs, mask=voters)
                 if model is None or n_fit < MIN_MATCHES_AFFINE:      # too few or degenerate: the host path, from its gathers on
                     on_device, rms = False, None
-                    g0, g1 = gathered()
-                    if voters is not None:
-                        g0, g1 = g0[voters], g1[voters]
+                    if not dev_median:
+                        g0, g1 = gathered_voters()
                         n_pairs = g0.shape[0]
             enough = n_pairs >= MIN_MATCHES_AFFINE
             if on_device:
@@ -343,10 +362,19 @@ class LinearAlign(object):
                 matrix, offset = numpy.array([[e, d], [b, a]], dtype=numpy.float32), numpy.array([f, c], dtype=numpy.float32)
             elif shift_only or not enough:
                 (logger.debug if shift_only else logger.warning)("Shift Only mode: Common keypoints: %s" % n_pairs)
-                matrix, offset = self._median_shift(g0, g1)
+                if dev_median:
+                    moved = self.match.shift(ref_list, self.sift.device_records(), pairs, mask=voters)[0]
+                    mdx, mdy = moved if moved is not None else (numpy.nan, numpy.nan)
+                    matrix, offset = numpy.identity(2, dtype=numpy.float32), numpy.array([mdy, mdx], numpy.float32)
+                else:
+                    matrix, offset = self._median_shift(g0, g1)
             else:
                 logger.debug("Common keypoints: %s" % n_pairs)
+                if g0 is None:                      # median="device" with enough pairs for the host's affine fit
+                    g0, g1 = gathered_voters()
                 matrix, offset = self._affine(g0, g1)
+            if return_all and rms is None and g0 is None:       # rms below is taken from the gathers (made before `relative`
+                g0, g1 = gathered_voters()                      # replaces the reference the pairs index)
             if double_check and enough:
                 logger.warning("Validating keypoints, %s,%s" % (matrix, offset))
                 keep = self._inliers(g0, g1)

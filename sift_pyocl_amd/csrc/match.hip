@@ -1,6 +1,7 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) and the least-squares affine map of the pairs (k_fit.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp) and their exact median displacement (k_shift.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <new>
 
@@ -12,6 +13,7 @@
 #include "k_knn_window.hpp"
 #include "k_consensus.hpp"
 #include "k_fit.hpp"
+#include "k_shift.hpp"
 
 using namespace siftk;
 
@@ -68,6 +70,11 @@ struct siftmi_matcher {
     uint8_t *f_mask = nullptr;
     int64_t cap_f_mask = 0;
     FitPartials *f_part = nullptr;
+    // median displacement (siftmi_match_shift): the pairs' keys and the select's counters; on demand.  A host mask is staged in
+    // f_mask, the positions in c_pts and a keep mask in c_mask, as the calls above do
+    uint2 *s_keys = nullptr;
+    int64_t cap_s_keys = 0;
+    ShiftScratch *s_scratch = nullptr;
 };
 
 namespace {
@@ -127,7 +134,7 @@ int siftmi_match_destroy(siftmi_matcher *m) {
     for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
                     (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result,
                     (void *)m->w_cells, (void *)m->w_work, (void *)m->w_desc, (void *)m->w_meta, (void *)m->w_order,
-                    (void *)m->knn_keys, (void *)m->knn_out, (void *)m->f_mask, (void *)m->f_part})
+                    (void *)m->knn_keys, (void *)m->knn_out, (void *)m->f_mask, (void *)m->f_part, (void *)m->s_keys, (void *)m->s_scratch})
         if (q) hipFree(q);
     if (m->ec_a) hipEventDestroy(m->ec_a);
     if (m->ec_b) hipEventDestroy(m->ec_b);
@@ -731,6 +738,80 @@ int siftmi_match_fit(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, 
     HIPCHK(hipGetLastError());
     if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
     memcpy(out, res, sizeof res);
+    return SIFTMI_OK;
+}
+
+namespace {
+// every launch of the median select (k_shift.hpp), in stream order: gather, keys + count + first digit, three passes, finish and,
+// with `keep`, the mask.  B workgroups for the kernels that walk the pairs; `sc` is cleared first.
+void launch_shift(hipStream_t st, int B, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const int2 *dp, int M, const uint8_t *dm,
+                  float4 *pts, uint2 *keys, ShiftScratch *sc, float tol, uint8_t *keep) {
+    const dim3 grid((unsigned)B), wg(SIFT_SHIFT_THREADS);
+    hipMemsetAsync(sc, 0, sizeof(ShiftScratch), st);
+    hipLaunchKernelGGL(consensus_gather_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, d1, n1, d2, n2, dp, M, pts);
+    hipLaunchKernelGGL(shift_key_kernel, grid, wg, 0, st, (const float4 *)pts, dm, M, keys, sc);
+    for (int p = 1; p <= 3; p++) hipLaunchKernelGGL(shift_pass_kernel, grid, wg, 0, st, (const uint2 *)keys, M, p, sc);
+    hipLaunchKernelGGL(shift_finish_kernel, dim3(1), wg, 0, st, sc);
+    if (keep) hipLaunchKernelGGL(shift_keep_kernel, grid, wg, 0, st, (const uint2 *)keys, M, tol, keep, sc);
+}
+}  // namespace
+
+// Exact median displacement of the pairs of a match (k_shift.hpp; the contract is DESIGN.md section 7 row 11).  The lists, the
+// pairs and the mask are used where they lie; host ones are staged in the matcher's own buffers.
+int siftmi_match_shift(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                       const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device,
+                       const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
+                       const uint8_t *mask, int32_t mask_is_device, int32_t blocks,
+                       float tol, uint8_t *keep, float *out, int64_t *counts, double *kernel_ms) {
+    if (!m || !out || !counts) return fail(SIFTMI_EINVAL, "null argument");
+    if (n1 < 0 || n2 < 0 || n_pairs < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff || n_pairs > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n_pairs > 0 && !pairs) return fail(SIFTMI_EINVAL, "null pairs with %lld pairs", (long long)n_pairs);
+    if (blocks < 0 || blocks > SIFT_FIT_MAX_BLOCKS) return fail(SIFTMI_EINVAL, "blocks %d outside 0..%d", blocks, SIFT_FIT_MAX_BLOCKS);
+    if (keep && !(tol >= 0.f)) return fail(SIFTMI_EINVAL, "tol must be >= 0 (+inf is allowed) with a keep mask");
+    HIPCHK(hipSetDevice(m->device));
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (n_pairs == 0) {     // EMPTY, nothing is launched
+        for (int k = 0; k < SIFT_SHIFT_OUT; k++) out[k] = std::nanf("");
+        counts[0] = counts[1] = 0;
+        return SIFTMI_OK;
+    }
+    if (kp1_is_device || kp2_is_device || pairs_is_device || (mask && mask_is_device)) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2, *dm = mask;
+    const int2 *dp = (const int2 *)pairs;
+    int rc;
+    if (!kp1_is_device && n1 > 0 && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (!kp2_is_device && n2 > 0 && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (!pairs_is_device) {
+        if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, n_pairs, sizeof(int2)))) return rc;
+        HIPCHK(hipMemcpyAsync(m->pairs, pairs, (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, m->stream));
+        dp = m->pairs;
+    }
+    if (mask && !mask_is_device) {
+        if ((rc = ensure((void **)&m->f_mask, &m->cap_f_mask, n_pairs, 1))) return rc;
+        HIPCHK(hipMemcpyAsync(m->f_mask, mask, (size_t)n_pairs, hipMemcpyHostToDevice, m->stream));
+        dm = m->f_mask;
+    }
+    if ((rc = ensure((void **)&m->c_pts, &m->cap_c_pts, n_pairs, sizeof(float4))) ||
+        (rc = ensure((void **)&m->s_keys, &m->cap_s_keys, n_pairs, sizeof(uint2)))) return rc;
+    if (keep && (rc = ensure((void **)&m->c_mask, &m->cap_c_mask, n_pairs, 1))) return rc;
+    if (!m->s_scratch) HIPCHK(hipMalloc((void **)&m->s_scratch, sizeof(ShiftScratch)));
+    const int M = (int)n_pairs;
+    // fit's rule: a workgroup per 256 pairs up to 256 workgroups, one per CU; beyond that a lane owns several pairs
+    int B = blocks;
+    if (B == 0) { B = (M + SIFT_SHIFT_THREADS - 1) / SIFT_SHIFT_THREADS; if (B > 256) B = 256; if (B < 1) B = 1; }
+    hipEventRecord(m->ec_a, m->stream);
+    launch_shift(m->stream, B, d1, (int)n1, d2, (int)n2, dp, M, dm, m->c_pts, m->s_keys, m->s_scratch, tol, keep ? m->c_mask : nullptr);
+    hipEventRecord(m->ec_b, m->stream);
+    struct { unsigned int n, n_keep; float out[SIFT_SHIFT_OUT]; } res;      // the tail of ShiftScratch
+    static_assert(sizeof res == sizeof(ShiftScratch) - offsetof(ShiftScratch, n), "the results are the last members of ShiftScratch");
+    HIPCHK(hipMemcpyAsync(&res, &m->s_scratch->n, sizeof res, hipMemcpyDeviceToHost, m->stream));
+    if (keep) HIPCHK(hipMemcpyAsync(keep, m->c_mask, (size_t)M, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
+    memcpy(out, res.out, sizeof res.out);
+    counts[0] = res.n; counts[1] = keep ? res.n_keep : 0;
     return SIFTMI_OK;
 }
 

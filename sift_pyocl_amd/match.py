@@ -243,6 +243,55 @@ class MatchPlan(object):
         result = (raw[13:19].copy() if ok else None, float(numpy.sqrt(raw[19] / raw[1])) if ok else float("nan"), int(raw[1]))
         return result + (raw,) if return_moments else result
 
+    def shift(self, kp1, kp2, pairs, mask=None, tol=None, blocks=0, return_ranks=False):
+        """Median displacement of the ``kp2`` positions of the pairs against their ``kp1`` positions, computed on the device
+        (extension; what ``numpy.median`` gives ``LinearAlign``'s translation-only estimate on the host).  Exact: per axis the
+        two middle float32 displacements are selected in the total order of float32 and averaged as ``numpy.median`` does, so
+        the value is numpy's bit for bit, up to the sign of a zero.  A pair with an index outside
+        its list or a non-finite coordinate is skipped.
+
+        :param kp1, kp2: the keypoint lists ``pairs`` indexes, numpy records or device tensors as for ``match``
+        :param pairs: (M, 2) int32 indices, a numpy array or a device tensor
+        :param mask: None, or (M,) bool / uint8, a numpy array or a device tensor: only the pairs with a non-zero entry count
+                     (the mask of ``consensus``)
+        :param tol: None, or a distance in pixels >= 0 (``inf`` is allowed): the result gains the bool (M,) mask of the counted
+                    pairs whose displacement lies within ``tol`` of the median on both axes (float32)
+        :param blocks: workgroups the pairs are spread over, 1 .. 1024; 0 picks by M.  The result does not depend on it
+        :return: ``((dx, dy), n)``: two ``numpy.float32`` and the number of pairs counted; ``(None, 0)`` when no pair is usable.
+                 With ``tol`` a third item, the keep mask; with ``return_ranks`` a last item, the six float32 values of
+                 ``siftmi_match_shift`` (dx, dy, then the lower and upper middle displacement of x and of y; NaN without a pair).
+        """
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        pp, devp, pdtype, pshape, keepp = _pointer_of(pairs)
+        if pdtype != numpy.int32 or len(pshape) != 2 or pshape[1] != 2:
+            raise RuntimeError("pairs must be an (M, 2) int32 array")
+        n_pairs = int(pshape[0])
+        pm, devm, keepm = None, 0, None
+        if mask is not None:
+            if isinstance(mask, numpy.ndarray) and mask.dtype == numpy.bool_:
+                mask = mask.view(numpy.uint8)
+            pm, devm, mdtype, mshape, keepm = _pointer_of(mask)
+            if mdtype.itemsize != 1 or mdtype.kind not in "bu" or tuple(mshape) != (n_pairs,):
+                raise RuntimeError("mask must be an (M,) bool or uint8 array")
+        raw = numpy.empty(6, numpy.float32)
+        counts = numpy.zeros(2, numpy.int64)
+        kept = numpy.zeros(n_pairs, numpy.uint8) if tol is not None else None
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_shift(self._handle, p1, n1, dev1, p2, n2, dev2, pp if n_pairs else None, n_pairs, devp,
+                                                     pm if n_pairs else None, devm, int(blocks), C.c_float(0.0 if tol is None else tol),
+                                                     kept.ctypes.data if tol is not None else None, raw.ctypes.data,
+                                                     counts.ctypes.data, C.byref(ms)))
+            if self.profile:
+                from .plan import StageEvent
+                self.events.append(("shift", StageEvent(ms.value)))          # device time, gather to the last kernel
+        n = int(counts[0])
+        result = ((raw[0], raw[1]) if n else None, n)
+        if tol is not None:
+            result += (kept.view(numpy.bool_),)
+        return result + (raw,) if return_ranks else result
+
     KNN_MAX = 8
 
     KNN_METRICS = {"l1": _lib.METRIC_L1, "l2": _lib.METRIC_L2SQ}
