@@ -379,6 +379,33 @@ int siftmi_match_shift(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1
                        const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device,
                        const uint8_t *mask, int32_t mask_is_device, int32_t blocks,
                        float tol, uint8_t *keep, float *out, int64_t *counts, double *kernel_ms);
+/* siftmi_match over a batch of S segment pairs in one set of launches and one stream synchronisation (extension; DESIGN.md section 7
+ * row 12, restated in numpy by tests/match_batch_ref.py).  kp2 holds the records of S lists back to back, counts2[s] of them in
+ * segment s; kp1 likewise with counts1, or, with counts1 == NULL, ONE list of n1 records that every segment is matched against.
+ * Segment s gets the rule of `matching` (matching_cpu.cl:57-109) on its own two lists: ascending j, strict '<' (the earliest index of
+ * the minimum wins, dist2 is the second smallest of the multiset), pair kept iff dist2 != 0 && dist1 / dist2 < ratio_th in f32 with
+ * both distances starting at 1e12f -- siftmi_match_ex with roi_mode 0 on the two segments.  Indices are local to the segment.
+ * The pairs of segment s are the rows [sum(pair_counts[0..s)), + pair_counts[s]) of `pairs`, in ascending i: the order is fixed
+ * (a query gives at most one pair), and the result does not depend on part_len or on scheduling.  A segment with an empty list on
+ * either side gives no pair; one whose second list has one element pairs every query with it.
+ *   mutual       keep (i, j) only if i is also the nearest element of segment s's first list to j, ties to the smallest i
+ *                (siftmi_match_ex's rule); with a shared first list, the nearest of the whole list
+ *   part_len     elements of a second-list segment per partition of the scan: 0 (chosen so that the whole batch gives about 2048
+ *                workgroups) or a multiple of 64 up to 65 472 (test hook)
+ *   pairs        room for one row of 2 int32 per query of the first side: n1 rows, or n_segments * n1 with a shared list; host, or
+ *                device (pairs_is_device: the rows are written where they lie and nothing but pair_counts comes back)
+ *   pair_counts  host, n_segments int64, written by every call that returns SIFTMI_OK
+ * Both lists are used where they lie (host lists are staged).  The region of interest plays no part and the matcher's pair
+ * capacity (`size`) is left alone.  When no segment has an element on both sides nothing is launched.
+ * siftmi_match_last_kernel_ms reports all kernels of the call, siftmi_match_last_stage_ms its stages as for siftmi_match.
+ * SIFTMI_EINVAL, nothing launched: n_segments outside 0 .. 65 535, a negative count, counts that do not add up to n1 / n2, a
+ * ratio_th that is not <= 1 (above 1 the rule pairs a query without a candidate with index 0), a part_len that is not as above,
+ * a null list, counts2, pair_counts or pairs where it is needed, more than 2^31 - 1 queries, or more work than the tables hold
+ * (2^22 workgroups a direction, 2^31 - 1 partial results). */
+int siftmi_match_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                       const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                       const int64_t *counts1, const int64_t *counts2, float ratio_th, int32_t mutual, int32_t part_len,
+                       int32_t *pairs, int32_t pairs_is_device, int64_t *pair_counts);
 int siftmi_match_last_kernel_ms(const siftmi_matcher *plan, float *ms);
 /* profile != 0 at creation: device time in ms of the last call's stages, in the order of the events the reference
  * appends under profile=True (sift-src/match.py:226-263): ms4[0] "copy H->D KP_1", [1] "copy H->D KP_2", [2] "matching",

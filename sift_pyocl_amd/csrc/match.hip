@@ -1,5 +1,5 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp) and their exact median displacement (k_shift.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp), their exact median displacement (k_shift.hpp) and the matcher over a batch of segment pairs (k_match_batch.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -14,6 +14,7 @@
 #include "k_consensus.hpp"
 #include "k_fit.hpp"
 #include "k_shift.hpp"
+#include "k_match_batch.hpp"
 
 using namespace siftk;
 
@@ -75,6 +76,13 @@ struct siftmi_matcher {
     uint2 *s_keys = nullptr;
     int64_t cap_s_keys = 0;
     ShiftScratch *s_scratch = nullptr;
+    // batch matching (siftmi_match_batch): the tables in pinned host memory (followed by the segments' scan values, which come
+    // back there) and on the device, and the integer scratch of the compaction (dense results, the blocks' sums and offsets, the
+    // segments' scan values); on demand.  The partials, `nearest` and, for a host result, `pairs` are the ones above
+    uint8_t *mb_host = nullptr, *mb_tab = nullptr;
+    int64_t cap_mb_host = 0, cap_mb_tab = 0;
+    int *mb_ints = nullptr;
+    int64_t cap_mb_ints = 0;
 };
 
 namespace {
@@ -134,8 +142,10 @@ int siftmi_match_destroy(siftmi_matcher *m) {
     for (void *q : {(void *)m->roi, (void *)m->q1, (void *)m->l1, (void *)m->q2, (void *)m->l2, (void *)m->nearest, (void *)m->pairs2,
                     (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result,
                     (void *)m->w_cells, (void *)m->w_work, (void *)m->w_desc, (void *)m->w_meta, (void *)m->w_order,
-                    (void *)m->knn_keys, (void *)m->knn_out, (void *)m->f_mask, (void *)m->f_part, (void *)m->s_keys, (void *)m->s_scratch})
+                    (void *)m->knn_keys, (void *)m->knn_out, (void *)m->f_mask, (void *)m->f_part, (void *)m->s_keys, (void *)m->s_scratch,
+                    (void *)m->mb_tab, (void *)m->mb_ints})
         if (q) hipFree(q);
+    if (m->mb_host) hipHostFree(m->mb_host);
     if (m->ec_a) hipEventDestroy(m->ec_a);
     if (m->ec_b) hipEventDestroy(m->ec_b);
     if (m->counter) hipFree(m->counter);
@@ -812,6 +822,176 @@ int siftmi_match_shift(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1
     if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
     memcpy(out, res.out, sizeof res.out);
     counts[0] = res.n; counts[1] = keep ? res.n_keep : 0;
+    return SIFTMI_OK;
+}
+
+// The matcher over a batch of segment pairs (k_match_batch.hpp; the contract is DESIGN.md section 7 row 12)
+namespace {
+// one side of the batch: S lists back to back with their counts, or (counts == NULL) ONE list of `shared` records for every segment
+struct MbSide { const int64_t *counts; int64_t shared; };
+inline int64_t mb_count(const MbSide &s, int k) { return s.counts ? s.counts[k] : s.shared; }
+inline int64_t mb_qblocks(int64_t nq) { return (nq + SIFT_MB_QBLOCK - 1) / SIFT_MB_QBLOCK; }
+
+// elements per partition, one length for the whole batch: about 2048 workgroups over all segments together, a whole number of
+// tiles, at least four of them (match_direction's rule) and at most SIFT_MATCH_MAX_PART (the 16-bit index)
+int mb_part_len(const MbSide &q, const MbSide &l, int S) {
+    int64_t work = 0;
+    for (int s = 0; s < S; s++) work += mb_qblocks(mb_count(q, s)) * mb_count(l, s);
+    int64_t len = (work + 2047) / 2048;
+    len = (len + SIFT_MATCH_TILE - 1) / SIFT_MATCH_TILE * SIFT_MATCH_TILE;
+    if (len < 4 * SIFT_MATCH_TILE) len = 4 * SIFT_MATCH_TILE;
+    if (len > SIFT_MATCH_MAX_PART) len = SIFT_MATCH_MAX_PART;
+    return (int)len;
+}
+// entries of the two tables and partials of one direction
+struct MbSizes { int64_t work, blocks, partials; };
+MbSizes mb_sizes(const MbSide &q, const MbSide &l, int S, int len) {
+    MbSizes z = {0, 0, 0};
+    for (int s = 0; s < S; s++) {
+        const int64_t nq = mb_count(q, s), np = (mb_count(l, s) + len - 1) / len;
+        z.blocks += mb_qblocks(nq); z.work += mb_qblocks(nq) * np; z.partials += np * nq;
+    }
+    return z;
+}
+// the tables of one direction, segments in order, a segment's blocks in order; seg_block (may be null): S + 1 first blocks
+void mb_fill(const MbSide &q, const MbSide &l, int S, int len, MbWork *work, MbBlock *blocks, int *seg_block) {
+    int64_t qoff = 0, loff = 0, pbase = 0, e = 0, w = 0;
+    for (int s = 0; s < S; s++) {
+        const int64_t nq = mb_count(q, s), nl = mb_count(l, s), np = (nl + len - 1) / len;
+        if (seg_block) seg_block[s] = (int)e;
+        for (int64_t b0 = 0; b0 < nq; b0 += SIFT_MB_QBLOCK) {
+            const int qc = (int)(nq - b0 < SIFT_MB_QBLOCK ? nq - b0 : SIFT_MB_QBLOCK);
+            blocks[e++] = {qc, (int)(pbase + b0), (int)nq, (int)np, (int)b0, (int)loff, (int)(qoff + b0), 0};
+            for (int64_t p = 0; p < np; p++) {
+                const int64_t lf = loff + p * len, le = (p + 1) * len < nl ? lf + len : loff + nl;
+                work[w++] = {(int)(qoff + b0), qc, (int)lf, (int)le, (int)(p * len), (int)(pbase + p * nq + b0), 0, 0};
+            }
+        }
+        pbase += np * nq;
+        if (q.counts) qoff += nq;
+        if (l.counts) loff += nl;
+    }
+    if (seg_block) seg_block[S] = (int)e;
+}
+int ensure_pinned(uint8_t **ptr, int64_t *cap, int64_t need) {
+    if (need <= *cap && *ptr) return SIFTMI_OK;
+    if (*ptr) hipHostFree(*ptr);
+    *ptr = nullptr; *cap = 0;
+    hipError_t e = hipHostMalloc((void **)ptr, (size_t)(need > 0 ? need : 1), hipHostMallocDefault);
+    if (e != hipSuccess) return fail(SIFTMI_ENOMEM, "hipHostMalloc(%lld): %s", (long long)need, hipGetErrorString(e));
+    *cap = need;
+    return SIFTMI_OK;
+}
+
+void launch_mb_partial(hipStream_t st, int n_work, const uint8_t *dq, const uint8_t *dl, const MbWork *work, MatchPartial *partial) {
+    hipLaunchKernelGGL(mb_partial_kernel, dim3((unsigned)n_work), dim3(256), 0, st, dq, dl, work, partial);
+}
+void launch_mb_merge(hipStream_t st, int n_blocks, const MatchPartial *partial, const MbBlock *blocks, float ratio_th, int *dense, int *sums,
+                     const int *nearest_in, int *nearest_out) {
+    hipLaunchKernelGGL(mb_merge_kernel, dim3((unsigned)n_blocks), dim3(256), 0, st, partial, blocks, ratio_th, dense, sums, nearest_in, nearest_out);
+}
+void launch_mb_scan(hipStream_t st, const int *sums, int n_blocks, int *offs, const int *seg_block, int S, int *seg_off) {
+    hipLaunchKernelGGL(mb_scan_kernel, dim3(1), dim3(SIFT_MB_SCAN_THREADS), 0, st, sums, n_blocks, offs, seg_block, S, seg_off);
+}
+void launch_mb_scatter(hipStream_t st, int n_blocks, const int *dense, const int *offs, const MbBlock *blocks, int2 *pairs) {
+    hipLaunchKernelGGL(mb_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, st, dense, offs, blocks, pairs);
+}
+}  // namespace
+
+int siftmi_match_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                       const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                       const int64_t *counts1, const int64_t *counts2, float ratio_th, int32_t mutual, int32_t part_len,
+                       int32_t *pairs, int32_t pairs_is_device, int64_t *pair_counts) {
+    if (!m) return fail(SIFTMI_EINVAL, "null argument");
+    if (n_segments < 0 || n_segments > SIFT_MB_MAX_SEGMENTS) return fail(SIFTMI_EINVAL, "n_segments %d outside 0..%d", n_segments, SIFT_MB_MAX_SEGMENTS);
+    if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n_segments > 0 && (!counts2 || !pair_counts)) return fail(SIFTMI_EINVAL, "null counts2 or pair_counts with %d segments", n_segments);
+    if (!(ratio_th <= 1.0f)) return fail(SIFTMI_EINVAL, "ratio_th must be <= 1, not %g", ratio_th);
+    if (part_len < 0 || part_len > SIFT_MATCH_MAX_PART || part_len % SIFT_MATCH_TILE)
+        return fail(SIFTMI_EINVAL, "part_len must be 0 or a multiple of %d up to %d, not %d", SIFT_MATCH_TILE, SIFT_MATCH_MAX_PART, part_len);
+    const int S = n_segments;
+    int64_t sum1 = 0, sum2 = 0;
+    for (int s = 0; s < S; s++) {
+        if (counts2[s] < 0 || (counts1 && counts1[s] < 0)) return fail(SIFTMI_EINVAL, "negative count in segment %d", s);
+        if (counts2[s] > n2 || (counts1 && counts1[s] > n1)) return fail(SIFTMI_EINVAL, "the count of segment %d exceeds its list", s);
+        sum2 += counts2[s]; sum1 += counts1 ? counts1[s] : 0;
+    }
+    if (sum2 != n2) return fail(SIFTMI_EINVAL, "counts2 add up to %lld, the second list has %lld records", (long long)sum2, (long long)n2);
+    if (counts1 && sum1 != n1) return fail(SIFTMI_EINVAL, "counts1 add up to %lld, the first list has %lld records", (long long)sum1, (long long)n1);
+    const int64_t NQ = counts1 ? n1 : (int64_t)S * n1;         // queries of the concatenated first side: the capacity of `pairs`
+    if (NQ > 0x7fffffff) return fail(SIFTMI_EINVAL, "%lld queries in all: more than 2^31 - 1", (long long)NQ);
+    HIPCHK(hipSetDevice(m->device));
+    for (float &v : m->stage_ms) v = -1.f;
+    m->last_ms = 0;
+    for (int s = 0; s < S; s++) pair_counts[s] = 0;
+    const MbSide side1 = {counts1, n1}, side2 = {counts2, n2};
+    const int len_f = part_len ? part_len : mb_part_len(side1, side2, S);
+    const MbSizes zf = mb_sizes(side1, side2, S, len_f);
+    if (zf.work == 0) return SIFTMI_OK;                        // no segment with an element on both sides: no pair, nothing is launched
+    if (!pairs) return fail(SIFTMI_EINVAL, "null pairs buffer");
+    const int len_r = !mutual ? 0 : part_len ? part_len : mb_part_len(side2, side1, S);
+    const MbSizes zr = mutual ? mb_sizes(side2, side1, S, len_r) : MbSizes{0, 0, 0};
+    const int64_t max_work = (int64_t)1 << 22;
+    if (zf.work > max_work || zr.work > max_work || zf.blocks * SIFT_MB_QBLOCK > 0x7fffffff || zf.partials > 0x7fffffff || zr.partials > 0x7fffffff)
+        return fail(SIFTMI_EINVAL, "the batch is too large: %lld + %lld workgroups, %lld + %lld partial results",
+                    (long long)zf.work, (long long)zr.work, (long long)zf.partials, (long long)zr.partials);
+    // the tables, one upload: scan entries forward / reverse, blocks forward / reverse, the segments' first blocks
+    const int64_t o_wf = 0, o_wr = o_wf + zf.work * (int64_t)sizeof(MbWork), o_bf = o_wr + zr.work * (int64_t)sizeof(MbWork),
+                  o_br = o_bf + zf.blocks * (int64_t)sizeof(MbBlock), o_sb = o_br + zr.blocks * (int64_t)sizeof(MbBlock),
+                  tab_bytes = o_sb + (S + 1) * (int64_t)sizeof(int);
+    const int Ef = (int)zf.blocks;
+    const int64_t i_sums = 0, i_offs = i_sums + Ef, i_seg = i_offs + Ef + 1, i_dense = (i_seg + S + 1 + 1) / 2 * 2, n_ints = i_dense + (int64_t)Ef * SIFT_MB_QBLOCK;
+    int rc;
+    if ((rc = ensure_pinned(&m->mb_host, &m->cap_mb_host, tab_bytes + (S + 1) * (int64_t)sizeof(int))) ||
+        (rc = ensure((void **)&m->mb_tab, &m->cap_mb_tab, tab_bytes, 1)) ||
+        (rc = ensure((void **)&m->mb_ints, &m->cap_mb_ints, n_ints, sizeof(int))) ||
+        (rc = ensure((void **)&m->partial, &m->cap_partial, zf.partials > zr.partials ? zf.partials : zr.partials, sizeof(MatchPartial)))) return rc;
+    if (mutual && (rc = ensure((void **)&m->nearest, &m->cap_nearest, n2, sizeof(int)))) return rc;
+    if (!pairs_is_device && (rc = ensure((void **)&m->pairs, &m->cap_pairs, NQ, sizeof(int2)))) return rc;
+    mb_fill(side1, side2, S, len_f, (MbWork *)(m->mb_host + o_wf), (MbBlock *)(m->mb_host + o_bf), (int *)(m->mb_host + o_sb));
+    if (mutual) mb_fill(side2, side1, S, len_r, (MbWork *)(m->mb_host + o_wr), (MbBlock *)(m->mb_host + o_br), nullptr);
+    int *seg_off_host = (int *)(m->mb_host + tab_bytes);
+    if (kp1_is_device || kp2_is_device || pairs_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    const bool prof = m->profile && m->ev[0];
+    if (prof) hipEventRecord(m->ev[0], m->stream);
+    if (!kp1_is_device && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (prof) hipEventRecord(m->ev[1], m->stream);
+    if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (prof) hipEventRecord(m->ev[2], m->stream);
+    HIPCHK(hipMemcpyAsync(m->mb_tab, m->mb_host, (size_t)tab_bytes, hipMemcpyHostToDevice, m->stream));
+    int *sums = m->mb_ints + i_sums, *offs = m->mb_ints + i_offs, *seg_off = m->mb_ints + i_seg, *dense = m->mb_ints + i_dense;
+    const MbBlock *blocks_f = (const MbBlock *)(m->mb_tab + o_bf);
+    int2 *result = pairs_is_device ? (int2 *)pairs : m->pairs;
+    hipEventRecord(m->ea, m->stream);
+    if (mutual) {
+        // reverse scan: the nearest element of its segment's first list for every record of the second side
+        launch_mb_partial(m->stream, (int)zr.work, d2, d1, (const MbWork *)(m->mb_tab + o_wr), m->partial);
+        launch_mb_merge(m->stream, (int)zr.blocks, m->partial, (const MbBlock *)(m->mb_tab + o_br), ratio_th, nullptr, nullptr, nullptr, m->nearest);
+    }
+    launch_mb_partial(m->stream, (int)zf.work, d1, d2, (const MbWork *)(m->mb_tab + o_wf), m->partial);
+    launch_mb_merge(m->stream, Ef, m->partial, blocks_f, ratio_th, dense, sums, mutual ? m->nearest : nullptr, nullptr);
+    launch_mb_scan(m->stream, sums, Ef, offs, (const int *)(m->mb_tab + o_sb), S, seg_off);
+    launch_mb_scatter(m->stream, Ef, dense, offs, blocks_f, result);
+    hipEventRecord(m->eb, m->stream);
+    HIPCHK(hipMemcpyAsync(seg_off_host, seg_off, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (!pairs_is_device) {
+        // the number of pairs is not known before the one wait: every row a query could have filled comes back
+        if (prof) hipEventRecord(m->ev[3], m->stream);
+        HIPCHK(hipMemcpyAsync(pairs, m->pairs, (size_t)NQ * sizeof(int2), hipMemcpyDeviceToHost, m->stream));
+        if (prof) hipEventRecord(m->ev[4], m->stream);
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    hipEventElapsedTime(&m->last_ms, m->ea, m->eb);
+    if (prof) {
+        m->stage_ms[2] = m->last_ms;
+        if (!kp1_is_device) hipEventElapsedTime(&m->stage_ms[0], m->ev[0], m->ev[1]);
+        if (!kp2_is_device) hipEventElapsedTime(&m->stage_ms[1], m->ev[1], m->ev[2]);
+        if (!pairs_is_device) hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
+    }
+    for (int s = 0; s < S; s++) pair_counts[s] = seg_off_host[s + 1] - seg_off_host[s];
     return SIFTMI_OK;
 }
 

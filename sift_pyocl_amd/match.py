@@ -372,6 +372,75 @@ class MatchPlan(object):
                 self.events += self._stage_events(self.KNN_STAGE_LABELS)
         return idx, dist
 
+    BATCH_MAX_SEGMENTS = 65535
+    BATCH_MAX_PART = 65472
+
+    def match_batch(self, kp1, counts1, kp2, counts2, ratio=None, mutual=False, part_len=0, out="host"):
+        """``match(kp1_s, kp2_s, raw_results=True)`` for S segment pairs in one call: one set of launches and one synchronisation
+        (extension).  ``kp2`` holds the records of S lists back to back -- the result of
+        ``BatchPlan.keypoints_batch_device`` is exactly this -- and ``counts2`` their lengths; ``kp1`` and ``counts1`` likewise, or
+        ``counts1=None`` for ONE list that every segment is matched against (the reference frame of a stack).  Matching each frame
+        against the one before it is two slices of one tensor with ``counts[:-1]`` and ``counts[1:]``.  Segment s gets ``match``'s
+        rule with the threshold ``float32(ratio ** 2)``, indices local to the segment; a segment with an empty list on either side
+        gives no pair, one whose second list has one element pairs every query with it.  The region of interest, windows and the
+        plan's ``kpsize`` play no part.
+
+        :param kp1, kp2: numpy records or device tensors of 144-byte records, as for ``match``
+        :param counts1: None, or S non-negative ints that add up to the records of ``kp1``
+        :param counts2: S non-negative ints that add up to the records of ``kp2``; S <= 65 535
+        :param ratio: None (``par.MatchRatio``) or a number with ``ratio ** 2 <= 1``, as for ``ratio_filter``
+        :param mutual: keep (i, j) only if i is also the nearest of j inside the segment (``match(mutual=True)``'s rule)
+        :param part_len: elements of a second-list segment per partition of the scan: 0 (the library chooses) or a multiple of 64
+                         up to 65 472.  The result does not depend on it
+        :param out: ``"host"``: ``pairs`` is a numpy array; ``"device"``: a torch int32 tensor on the plan's device, whose slices
+                    can go straight into ``consensus``, ``fit`` and ``shift``
+        :return: ``(pairs, pair_counts)``: (M, 2) int32 and (S,) int64 (numpy either way).  The pairs of segment s are the rows
+                 ``pairs[sum(pair_counts[:s]):][:pair_counts[s]]``; segments in order, ascending i inside a segment: the array
+                 is fixed completely
+        """
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        r = par.MatchRatio if ratio is None else ratio
+        th = numpy.float32(r * r)
+        if not th <= numpy.float32(1):
+            raise ValueError("ratio ** 2 must be <= 1, not %r" % (float(th),))
+        part_len = int(part_len)
+        if part_len < 0 or part_len > self.BATCH_MAX_PART or part_len % 64:
+            raise ValueError("part_len must be 0 or a multiple of 64 up to %d, not %d" % (self.BATCH_MAX_PART, part_len))
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        c2 = numpy.ascontiguousarray([int(c) for c in counts2], dtype=numpy.int64).reshape(-1)
+        S = len(c2)
+        c1 = None if counts1 is None else numpy.ascontiguousarray([int(c) for c in counts1], dtype=numpy.int64).reshape(-1)
+        if S > self.BATCH_MAX_SEGMENTS:
+            raise ValueError("%d segments: more than %d" % (S, self.BATCH_MAX_SEGMENTS))
+        if c1 is not None and len(c1) != S:
+            raise ValueError("counts1 has %d entries, counts2 %d" % (len(c1), S))
+        if (c2 < 0).any() or (c1 is not None and (c1 < 0).any()):
+            raise ValueError("negative count")
+        if int(c2.sum()) != n2 or (c1 is not None and int(c1.sum()) != n1):
+            raise ValueError("the counts do not add up to the lists: %s of %d and %d of %d records" %
+                             ("-" if c1 is None else int(c1.sum()), n1, int(c2.sum()), n2))
+        rows = n1 * S if c1 is None else n1
+        pair_counts = numpy.zeros(S, numpy.int64)
+        if out == "device":
+            import torch
+            pairs = torch.empty((rows, 2), dtype=torch.int32, device=torch.device("cuda", self.device))
+            pp = pairs.data_ptr()
+        else:
+            pairs = numpy.empty((rows, 2), dtype=numpy.int32)
+            pp = pairs.ctypes.data
+        if S == 0:
+            return pairs[:0], pair_counts
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_batch(self._handle, p1, n1, dev1, p2, n2, dev2, S, None if c1 is None else c1.ctypes.data,
+                                                     c2.ctypes.data, C.c_float(th), int(bool(mutual)), part_len, pp if rows else None,
+                                                     int(out == "device"), pair_counts.ctypes.data))
+            if self.profile:
+                self.events += self._stage_events()
+        total = int(pair_counts.sum())
+        return (pairs[:total] if out == "device" else pairs[:total].copy()), pair_counts
+
     def _records(self, kp):
         if isinstance(kp, numpy.ndarray):
             arr = numpy.ascontiguousarray(kp)
