@@ -406,6 +406,43 @@ int siftmi_match_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1
                        const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
                        const int64_t *counts1, const int64_t *counts2, float ratio_th, int32_t mutual, int32_t part_len,
                        int32_t *pairs, int32_t pairs_is_device, int64_t *pair_counts);
+/* siftmi_match_fit for every segment of a batch in one set of launches and one stream synchronisation (extension; DESIGN.md
+ * section 7 row 13, restated by tests/estimate_batch_ref.py).  The lists, n_segments, counts1 (NULL: one shared first list) and
+ * counts2 are siftmi_match_batch's arguments and `pairs` / `pair_counts` its results, unchanged: the pairs of segment s are the rows
+ * [sum(pair_counts[0..s)), + pair_counts[s]) with indices local to the segment.  Row r of segment s with (i, j) reads record
+ * off1_s + i of kp1 iff 0 <= i < counts1[s] (shared list: off1_s = 0, the count is n1) and record off2_s + j of kp2 iff
+ * 0 <= j < counts2[s]; otherwise it is four NaN and unused, so a record of a neighbouring segment is never read.  Segment s then gets
+ * siftmi_match_fit's arithmetic with pair index = the row's position inside the segment, B_s = blocks, or with blocks == 0
+ * min(256, max(1, ceil(pair_counts[s] / 256))), workgroups: the 20 doubles are bit for bit those of siftmi_match_fit on the
+ * segment's own lists, pairs, mask slice and `blocks`.  A segment without a pair is EMPTY and gets no workgroup.
+ * sum(pair_counts) == 0 (n_segments == 0 included): nothing launched, *kernel_ms = 0.  Lists, pairs and mask are used where they lie;
+ * host ones are staged.  SIFTMI_EINVAL, nothing launched, nothing written: a null matcher, n_segments outside 0 .. 65 535, a negative
+ * count, a count above 2^31 - 1, counts that do not add up to n1 / n2, pair_counts that do not add up to n_pairs, blocks outside
+ * 0..1024, more than 2^20 workgroups in all, a null list, pairs, counts2, pair_counts or out where it is needed.
+ *   mask       optional, n_pairs bytes aligned with the rows of `pairs`, non-zero = use the pair
+ *   out        host, n_segments * 20 doubles in siftmi_match_fit's order, all written by every call that returns SIFTMI_OK
+ *   kernel_ms  optional: hipEvent time from the first kernel to the last */
+int siftmi_match_fit_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                           const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                           const int64_t *counts1, const int64_t *counts2,
+                           const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device, const int64_t *pair_counts,
+                           const uint8_t *mask, int32_t mask_is_device, int32_t blocks, double *out, double *kernel_ms);
+/* siftmi_match_shift for every segment of a batch in one launch and one stream synchronisation.
+ * Arguments, gather rule, empty batches and errors as for siftmi_match_fit_batch; there is no `blocks`: one workgroup selects the
+ * medians of one segment, and a median does not depend on the launch shape.  The results of segment s are bit for bit those of
+ * siftmi_match_shift on the segment's own lists, pairs and mask slice.  Also SIFTMI_EINVAL: a null out or counts with a segment,
+ * and with a keep mask a tol that is NaN or negative.
+ *   tol, keep  keep: optional, host, n_pairs bytes: siftmi_match_shift's rule with every row tested against the medians of its own
+ *              segment (a segment whose median is not finite keeps nothing); tol is ignored without keep
+ *   out        host, n_segments * 6 floats: mdx, mdy, lo_dx, hi_dx, lo_dy, hi_dy per segment; NaN where no pair is used
+ *   counts     host, n_segments * 2 int64: n and n_keep (0 without keep) per segment
+ *   kernel_ms  optional: hipEvent time of the kernel */
+int siftmi_match_shift_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                             const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                             const int64_t *counts1, const int64_t *counts2,
+                             const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device, const int64_t *pair_counts,
+                             const uint8_t *mask, int32_t mask_is_device, float tol, uint8_t *keep, float *out, int64_t *counts,
+                             double *kernel_ms);
 int siftmi_match_last_kernel_ms(const siftmi_matcher *plan, float *ms);
 /* profile != 0 at creation: device time in ms of the last call's stages, in the order of the events the reference
  * appends under profile=True (sift-src/match.py:226-263): ms4[0] "copy H->D KP_1", [1] "copy H->D KP_2", [2] "matching",

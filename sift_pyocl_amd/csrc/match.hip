@@ -1,5 +1,5 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp), their exact median displacement (k_shift.hpp) and the matcher over a batch of segment pairs (k_match_batch.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp), their exact median displacement (k_shift.hpp), the matcher over a batch of segment pairs (k_match_batch.hpp) and the fit and the median of every segment of such a batch at once (k_estimate_batch.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -15,6 +15,7 @@
 #include "k_fit.hpp"
 #include "k_shift.hpp"
 #include "k_match_batch.hpp"
+#include "k_estimate_batch.hpp"
 
 using namespace siftk;
 
@@ -83,6 +84,13 @@ struct siftmi_matcher {
     int64_t cap_mb_host = 0, cap_mb_tab = 0;
     int *mb_ints = nullptr;
     int64_t cap_mb_ints = 0;
+    // segmented fit and median (siftmi_match_fit_batch / siftmi_match_shift_batch): the tables in pinned host memory (followed by the
+    // per-segment results, which come back there) and on the device, the fit's partials and results, the median's results; on
+    // demand.  Lists, pairs, mask, positions, keys and keep bytes are staged in the buffers of the single calls above
+    uint8_t *eb_host = nullptr, *eb_tab = nullptr, *eb_res = nullptr;
+    int64_t cap_eb_host = 0, cap_eb_tab = 0, cap_eb_res = 0;
+    double *eb_f64 = nullptr;
+    int64_t cap_eb_f64 = 0;
 };
 
 namespace {
@@ -143,9 +151,10 @@ int siftmi_match_destroy(siftmi_matcher *m) {
                     (void *)m->c_pts, (void *)m->c_mask, (void *)m->c_valid, (void *)m->c_models, (void *)m->c_votes, (void *)m->c_result,
                     (void *)m->w_cells, (void *)m->w_work, (void *)m->w_desc, (void *)m->w_meta, (void *)m->w_order,
                     (void *)m->knn_keys, (void *)m->knn_out, (void *)m->f_mask, (void *)m->f_part, (void *)m->s_keys, (void *)m->s_scratch,
-                    (void *)m->mb_tab, (void *)m->mb_ints})
+                    (void *)m->mb_tab, (void *)m->mb_ints, (void *)m->eb_tab, (void *)m->eb_res, (void *)m->eb_f64})
         if (q) hipFree(q);
     if (m->mb_host) hipHostFree(m->mb_host);
+    if (m->eb_host) hipHostFree(m->eb_host);
     if (m->ec_a) hipEventDestroy(m->ec_a);
     if (m->ec_b) hipEventDestroy(m->ec_b);
     if (m->counter) hipFree(m->counter);
@@ -992,6 +1001,210 @@ int siftmi_match_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1
         if (!pairs_is_device) hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
     }
     for (int s = 0; s < S; s++) pair_counts[s] = seg_off_host[s + 1] - seg_off_host[s];
+    return SIFTMI_OK;
+}
+
+// The fit and the median of every segment of a batch at once (k_estimate_batch.hpp; the contract is DESIGN.md section 7 row 13)
+namespace {
+struct EbBatch {
+    const siftmi_keypoint *kp1; int64_t n1; int32_t dev1;
+    const siftmi_keypoint *kp2; int64_t n2; int32_t dev2;
+    int S;
+    const int64_t *counts1, *counts2;
+    const int32_t *pairs; int64_t n_pairs; int32_t devp;
+    const int64_t *pair_counts;
+    const uint8_t *mask; int32_t devm;
+};
+// everything that is wrong with the arguments both entries share; nothing touches the device
+int eb_validate(const siftmi_matcher *m, const EbBatch &a) {
+    if (!m) return fail(SIFTMI_EINVAL, "null argument");
+    if (a.S < 0 || a.S > SIFT_EB_MAX_SEGMENTS) return fail(SIFTMI_EINVAL, "n_segments %d outside 0..%d", a.S, SIFT_EB_MAX_SEGMENTS);
+    if (a.n1 < 0 || a.n2 < 0 || a.n_pairs < 0 || a.n1 > 0x7fffffff || a.n2 > 0x7fffffff || a.n_pairs > 0x7fffffff) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((a.n1 > 0 && !a.kp1) || (a.n2 > 0 && !a.kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (a.n_pairs > 0 && !a.pairs) return fail(SIFTMI_EINVAL, "null pairs with %lld pairs", (long long)a.n_pairs);
+    if (a.S > 0 && (!a.counts2 || !a.pair_counts)) return fail(SIFTMI_EINVAL, "null counts2 or pair_counts with %d segments", a.S);
+    int64_t sum1 = 0, sum2 = 0, sump = 0;
+    for (int s = 0; s < a.S; s++) {
+        if (a.counts2[s] < 0 || (a.counts1 && a.counts1[s] < 0) || a.pair_counts[s] < 0) return fail(SIFTMI_EINVAL, "negative count in segment %d", s);
+        if (a.counts2[s] > a.n2 || (a.counts1 && a.counts1[s] > a.n1) || a.pair_counts[s] > a.n_pairs)
+            return fail(SIFTMI_EINVAL, "a count of segment %d exceeds its list", s);
+        sum2 += a.counts2[s]; sum1 += a.counts1 ? a.counts1[s] : 0; sump += a.pair_counts[s];
+    }
+    if (sum2 != a.n2) return fail(SIFTMI_EINVAL, "counts2 add up to %lld, the second list has %lld records", (long long)sum2, (long long)a.n2);
+    if (a.counts1 && sum1 != a.n1) return fail(SIFTMI_EINVAL, "counts1 add up to %lld, the first list has %lld records", (long long)sum1, (long long)a.n1);
+    if (sump != a.n_pairs) return fail(SIFTMI_EINVAL, "pair_counts add up to %lld, there are %lld pairs", (long long)sump, (long long)a.n_pairs);
+    return SIFTMI_OK;
+}
+// fit's rule for one segment's workgroups; 0 for a segment without a pair
+inline int eb_blocks(int64_t rows, int blocks) {
+    if (rows == 0) return 0;
+    if (blocks) return blocks;
+    const int64_t B = (rows + SIFT_FIT_THREADS - 1) / SIFT_FIT_THREADS;
+    return (int)(B > 256 ? 256 : B);
+}
+// The tables, segments in order: `segs` gets entry b = 0 of every segment (all of them, or with `nonempty` only those with a pair),
+// `work` (may be null) the B_s entries of every segment.  Returns the entries written to `segs`.
+int eb_fill(const EbBatch &a, int blocks, bool nonempty, EbWork *segs, EbWork *work) {
+    int64_t off1 = 0, off2 = 0, row0 = 0, slot0 = 0, e = 0, w = 0;
+    for (int s = 0; s < a.S; s++) {
+        const int64_t rows = a.pair_counts[s], n1 = a.counts1 ? a.counts1[s] : a.n1, n2 = a.counts2[s];
+        const int B = eb_blocks(rows, blocks);
+        const EbWork head = {s, 0, B, (int)row0, (int)rows, (int)off1, (int)n1, (int)off2, (int)n2, (int)slot0};
+        if (B || !nonempty) segs[e++] = head;
+        if (work) for (int b = 0; b < B; b++) { work[w] = head; work[w++].b = b; }
+        row0 += rows; slot0 += B; off2 += n2;
+        if (a.counts1) off1 += n1;
+    }
+    return (int)e;
+}
+// the device synchronisation of the header's convention and the staging of host inputs, as in siftmi_match_fit
+int eb_stage(siftmi_matcher *m, const EbBatch &a, const uint8_t **d1, const uint8_t **d2, const int2 **dp, const uint8_t **dm) {
+    if (a.dev1 || a.dev2 || a.devp || (a.mask && a.devm)) HIPCHK(hipDeviceSynchronize());
+    *d1 = (const uint8_t *)a.kp1; *d2 = (const uint8_t *)a.kp2; *dp = (const int2 *)a.pairs; *dm = a.mask;
+    int rc;
+    if (!a.dev1 && a.n1 > 0 && (rc = stage_list(m, &m->kp1, &m->cap1, a.kp1, a.n1, d1))) return rc;
+    if (!a.dev2 && a.n2 > 0 && (rc = stage_list(m, &m->kp2, &m->cap2, a.kp2, a.n2, d2))) return rc;
+    if (!a.devp) {
+        if ((rc = ensure((void **)&m->pairs, &m->cap_pairs, a.n_pairs, sizeof(int2)))) return rc;
+        HIPCHK(hipMemcpyAsync(m->pairs, a.pairs, (size_t)a.n_pairs * sizeof(int2), hipMemcpyHostToDevice, m->stream));
+        *dp = m->pairs;
+    }
+    if (a.mask && !a.devm) {
+        if ((rc = ensure((void **)&m->f_mask, &m->cap_f_mask, a.n_pairs, 1))) return rc;
+        HIPCHK(hipMemcpyAsync(m->f_mask, a.mask, (size_t)a.n_pairs, hipMemcpyHostToDevice, m->stream));
+        *dm = m->f_mask;
+    }
+    return SIFTMI_OK;
+}
+
+void launch_eb_fit_pass1(hipStream_t st, int n_work, const uint8_t *d1, const uint8_t *d2, const int2 *dp, const uint8_t *dm, const EbWork *work,
+                         float4 *pts, const EbFitScratch &fs) {
+    hipLaunchKernelGGL(eb_fit_pass1_kernel, dim3((unsigned)n_work), dim3(SIFT_FIT_THREADS), 0, st, d1, d2, dp, dm, work, pts, fs);
+}
+void launch_eb_fit_pass2(hipStream_t st, int n_work, const float4 *pts, const uint8_t *dm, const EbWork *work, const EbFitScratch &fs) {
+    hipLaunchKernelGGL(eb_fit_pass2_kernel, dim3((unsigned)n_work), dim3(SIFT_FIT_THREADS), 0, st, pts, dm, work, fs);
+}
+void launch_eb_fit_pass3(hipStream_t st, int n_work, const float4 *pts, const uint8_t *dm, const EbWork *work, const EbFitScratch &fs) {
+    hipLaunchKernelGGL(eb_fit_pass3_kernel, dim3((unsigned)n_work), dim3(SIFT_FIT_THREADS), 0, st, pts, dm, work, fs);
+}
+void launch_eb_fit_finish(hipStream_t st, const EbWork *segs, int S, const EbFitScratch &fs) {
+    hipLaunchKernelGGL(eb_fit_finish_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, segs, S, fs);
+}
+void launch_eb_shift(hipStream_t st, int n_segs, const uint8_t *d1, const uint8_t *d2, const int2 *dp, const uint8_t *dm, const EbWork *segs,
+                     uint2 *keys, float tol, uint8_t *keep, float *out, long long *counts) {
+    hipLaunchKernelGGL(eb_shift_kernel, dim3((unsigned)n_segs), dim3(SIFT_SHIFT_THREADS), 0, st, d1, d2, dp, dm, segs, keys, tol, keep, out, counts);
+}
+}  // namespace
+
+int siftmi_match_fit_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                           const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                           const int64_t *counts1, const int64_t *counts2,
+                           const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device, const int64_t *pair_counts,
+                           const uint8_t *mask, int32_t mask_is_device, int32_t blocks, double *out, double *kernel_ms) {
+    const EbBatch a = {kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, n_segments, counts1, counts2, pairs, n_pairs, pairs_is_device,
+                       pair_counts, mask, mask_is_device};
+    int rc;
+    if ((rc = eb_validate(m, a))) return rc;
+    const int S = n_segments;
+    if (S > 0 && !out) return fail(SIFTMI_EINVAL, "null argument");
+    if (blocks < 0 || blocks > SIFT_FIT_MAX_BLOCKS) return fail(SIFTMI_EINVAL, "blocks %d outside 0..%d", blocks, SIFT_FIT_MAX_BLOCKS);
+    int64_t W = 0;
+    for (int s = 0; s < S; s++) W += eb_blocks(pair_counts[s], blocks);
+    if (W > SIFT_EB_MAX_WORK) return fail(SIFTMI_EINVAL, "%lld workgroups in all: more than %d", (long long)W, SIFT_EB_MAX_WORK);
+    HIPCHK(hipSetDevice(m->device));
+    if (kernel_ms) *kernel_ms = 0.0;
+    const auto empty_row = [](double *row) {
+        for (int k = 0; k < SIFT_FIT_OUT; k++) row[k] = std::nan("");
+        row[SIFT_FIT_STATUS] = 1.0; row[SIFT_FIT_N] = 0.0;
+    };
+    if (n_pairs == 0) {     // every segment EMPTY, nothing is launched
+        for (int s = 0; s < S; s++) empty_row(out + (size_t)s * SIFT_FIT_OUT);
+        return SIFTMI_OK;
+    }
+    // the tables, one upload: the workgroups' entries, then one entry per segment; behind them, on the host, the results
+    const int64_t o_work = 0, o_segs = o_work + W * (int64_t)sizeof(EbWork), tab_bytes = o_segs + S * (int64_t)sizeof(EbWork),
+                  res_bytes = (int64_t)S * SIFT_FIT_OUT * (int64_t)sizeof(double);
+    // the partials and the results: p1 [W][4], p2 [W][7], p3 [W], count [W], out [S][20], eight bytes each
+    const int64_t n_f64 = W * 13 + (int64_t)S * SIFT_FIT_OUT;
+    if ((rc = ensure_pinned(&m->eb_host, &m->cap_eb_host, tab_bytes + res_bytes)) ||
+        (rc = ensure((void **)&m->eb_tab, &m->cap_eb_tab, tab_bytes, 1)) ||
+        (rc = ensure((void **)&m->eb_f64, &m->cap_eb_f64, n_f64, sizeof(double))) ||
+        (rc = ensure((void **)&m->c_pts, &m->cap_c_pts, n_pairs, sizeof(float4)))) return rc;
+    eb_fill(a, blocks, false, (EbWork *)(m->eb_host + o_segs), (EbWork *)(m->eb_host + o_work));
+    const uint8_t *d1, *d2, *dm;
+    const int2 *dp;
+    if ((rc = eb_stage(m, a, &d1, &d2, &dp, &dm))) return rc;
+    HIPCHK(hipMemcpyAsync(m->eb_tab, m->eb_host, (size_t)tab_bytes, hipMemcpyHostToDevice, m->stream));
+    EbFitScratch fs;
+    fs.p1 = m->eb_f64; fs.p2 = fs.p1 + W * 4; fs.p3 = fs.p2 + W * 7;
+    fs.count = (unsigned long long *)(fs.p3 + W); fs.out = fs.p3 + 2 * W;
+    const EbWork *work = (const EbWork *)(m->eb_tab + o_work), *segs = (const EbWork *)(m->eb_tab + o_segs);
+    double *res = (double *)(m->eb_host + tab_bytes);
+    hipEventRecord(m->ec_a, m->stream);
+    launch_eb_fit_pass1(m->stream, (int)W, d1, d2, dp, dm, work, m->c_pts, fs);
+    launch_eb_fit_pass2(m->stream, (int)W, (const float4 *)m->c_pts, dm, work, fs);
+    launch_eb_fit_pass3(m->stream, (int)W, (const float4 *)m->c_pts, dm, work, fs);
+    launch_eb_fit_finish(m->stream, segs, S, fs);
+    hipEventRecord(m->ec_b, m->stream);
+    HIPCHK(hipMemcpyAsync(res, fs.out, (size_t)res_bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
+    memcpy(out, res, (size_t)res_bytes);
+    for (int s = 0; s < S; s++) if (pair_counts[s] == 0) empty_row(out + (size_t)s * SIFT_FIT_OUT);     // no workgroup wrote these
+    return SIFTMI_OK;
+}
+
+int siftmi_match_shift_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                             const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                             const int64_t *counts1, const int64_t *counts2,
+                             const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device, const int64_t *pair_counts,
+                             const uint8_t *mask, int32_t mask_is_device, float tol, uint8_t *keep, float *out, int64_t *counts,
+                             double *kernel_ms) {
+    const EbBatch a = {kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, n_segments, counts1, counts2, pairs, n_pairs, pairs_is_device,
+                       pair_counts, mask, mask_is_device};
+    int rc;
+    if ((rc = eb_validate(m, a))) return rc;
+    const int S = n_segments;
+    if (S > 0 && (!out || !counts)) return fail(SIFTMI_EINVAL, "null argument");
+    if (keep && !(tol >= 0.f)) return fail(SIFTMI_EINVAL, "tol must be >= 0 (+inf is allowed) with a keep mask");
+    HIPCHK(hipSetDevice(m->device));
+    if (kernel_ms) *kernel_ms = 0.0;
+    const auto empty_row = [&](int s) {
+        for (int k = 0; k < SIFT_SHIFT_OUT; k++) out[(size_t)s * SIFT_SHIFT_OUT + k] = std::nanf("");
+        counts[2 * (size_t)s] = counts[2 * (size_t)s + 1] = 0;
+    };
+    if (n_pairs == 0) {     // every segment EMPTY, nothing is launched
+        for (int s = 0; s < S; s++) empty_row(s);
+        return SIFTMI_OK;
+    }
+    // the table, one upload: one entry per segment with a pair; behind it, on the host, the results: counts [S][2], out [S][6]
+    const int64_t tab_bytes = S * (int64_t)sizeof(EbWork), cnt_bytes = (int64_t)S * 2 * (int64_t)sizeof(long long),
+                  res_bytes = cnt_bytes + (int64_t)S * SIFT_SHIFT_OUT * (int64_t)sizeof(float);
+    if ((rc = ensure_pinned(&m->eb_host, &m->cap_eb_host, tab_bytes + res_bytes)) ||
+        (rc = ensure((void **)&m->eb_tab, &m->cap_eb_tab, tab_bytes, 1)) ||
+        (rc = ensure((void **)&m->eb_res, &m->cap_eb_res, res_bytes, 1)) ||
+        (rc = ensure((void **)&m->s_keys, &m->cap_s_keys, n_pairs, sizeof(uint2)))) return rc;
+    if (keep && (rc = ensure((void **)&m->c_mask, &m->cap_c_mask, n_pairs, 1))) return rc;
+    const int E = eb_fill(a, 1, true, (EbWork *)m->eb_host, nullptr);
+    const uint8_t *d1, *d2, *dm;
+    const int2 *dp;
+    if ((rc = eb_stage(m, a, &d1, &d2, &dp, &dm))) return rc;
+    HIPCHK(hipMemcpyAsync(m->eb_tab, m->eb_host, (size_t)E * sizeof(EbWork), hipMemcpyHostToDevice, m->stream));
+    uint8_t *res = m->eb_host + tab_bytes;
+    hipEventRecord(m->ec_a, m->stream);
+    launch_eb_shift(m->stream, E, d1, d2, dp, dm, (const EbWork *)m->eb_tab, m->s_keys, tol, keep ? m->c_mask : nullptr,
+                    (float *)(m->eb_res + cnt_bytes), (long long *)m->eb_res);
+    hipEventRecord(m->ec_b, m->stream);
+    HIPCHK(hipMemcpyAsync(res, m->eb_res, (size_t)res_bytes, hipMemcpyDeviceToHost, m->stream));
+    if (keep) HIPCHK(hipMemcpyAsync(keep, m->c_mask, (size_t)n_pairs, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counts come back as they are");
+    memcpy(counts, res, (size_t)cnt_bytes);
+    memcpy(out, res + cnt_bytes, (size_t)(res_bytes - cnt_bytes));
+    for (int s = 0; s < S; s++) if (pair_counts[s] == 0) empty_row(s);      // no workgroup wrote these
     return SIFTMI_OK;
 }
 

@@ -441,6 +441,110 @@ class MatchPlan(object):
         total = int(pair_counts.sum())
         return (pairs[:total] if out == "device" else pairs[:total].copy()), pair_counts
 
+    BATCH_MAX_WORK = 1 << 20
+
+    def _estimate_batch_args(self, kp1, counts1, kp2, counts2, pairs, pair_counts, mask):
+        """the arguments ``fit_batch`` and ``shift_batch`` share, checked as ``match_batch`` checks its own"""
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        pp, devp, pdtype, pshape, keepp = _pointer_of(pairs)
+        if pdtype != numpy.int32 or len(pshape) != 2 or pshape[1] != 2:
+            raise RuntimeError("pairs must be an (M, 2) int32 array")
+        n_pairs = int(pshape[0])
+        pm, devm, keepm = None, 0, None
+        if mask is not None:
+            if isinstance(mask, numpy.ndarray) and mask.dtype == numpy.bool_:
+                mask = mask.view(numpy.uint8)
+            pm, devm, mdtype, mshape, keepm = _pointer_of(mask)
+            if mdtype.itemsize != 1 or mdtype.kind not in "bu" or tuple(mshape) != (n_pairs,):
+                raise RuntimeError("mask must be an (M,) bool or uint8 array")
+        c2 = numpy.ascontiguousarray([int(c) for c in counts2], dtype=numpy.int64).reshape(-1)
+        S = len(c2)
+        c1 = None if counts1 is None else numpy.ascontiguousarray([int(c) for c in counts1], dtype=numpy.int64).reshape(-1)
+        pc = numpy.ascontiguousarray([int(c) for c in pair_counts], dtype=numpy.int64).reshape(-1)
+        if S > self.BATCH_MAX_SEGMENTS:
+            raise ValueError("%d segments: more than %d" % (S, self.BATCH_MAX_SEGMENTS))
+        if c1 is not None and len(c1) != S:
+            raise ValueError("counts1 has %d entries, counts2 %d" % (len(c1), S))
+        if len(pc) != S:
+            raise ValueError("pair_counts has %d entries, counts2 %d" % (len(pc), S))
+        if (c2 < 0).any() or (c1 is not None and (c1 < 0).any()) or (pc < 0).any():
+            raise ValueError("negative count")
+        if int(c2.sum()) != n2 or (c1 is not None and int(c1.sum()) != n1):
+            raise ValueError("the counts do not add up to the lists: %s of %d and %d of %d records" %
+                             ("-" if c1 is None else int(c1.sum()), n1, int(c2.sum()), n2))
+        if int(pc.sum()) != n_pairs:
+            raise ValueError("pair_counts add up to %d, there are %d pairs" % (int(pc.sum()), n_pairs))
+        args = (self._handle, p1, n1, dev1, p2, n2, dev2, S, None if c1 is None else c1.ctypes.data, c2.ctypes.data,
+                pp if n_pairs else None, n_pairs, devp, pc.ctypes.data, pm if n_pairs else None, devm)
+        return args, S, n_pairs, pc, (keep1, keep2, keepp, keepm, c1, c2)
+
+    def fit_batch(self, kp1, counts1, kp2, counts2, pairs, pair_counts, mask=None, blocks=0, return_moments=False):
+        """``fit(kp1_s, kp2_s, pairs_s, mask_s, blocks)`` for the S segments of a ``match_batch`` in one call: one set of launches and
+        one synchronisation, every result bit for bit that of the single call (extension).  The first
+        four arguments are ``match_batch``'s, ``pairs`` and ``pair_counts`` its results unchanged (indices local to the segment).
+        An index outside its segment's own list makes the pair unused; a record of a neighbouring segment is never read.
+
+        :param kp1, counts1, kp2, counts2: as for ``match_batch`` (``counts1=None``: one shared first list)
+        :param pairs: (M, 2) int32 indices, a numpy array or a device tensor
+        :param pair_counts: S non-negative ints that add up to M
+        :param mask: None, or (M,) bool / uint8 aligned with the rows of ``pairs``, a numpy array or a device tensor
+        :param blocks: workgroups per segment, 1 .. 1024 (part of the summation order); 0 picks by the segment's pairs as ``fit`` does
+        :return: ``(models, rms, n)``: float64 (S, 6) with NaN rows where a segment has no usable pair or is degenerate, float64
+                 (S,) ``sqrt(ssr / n)`` (NaN in those rows) and int64 (S,).  With ``return_moments`` a fourth item: float64 (S, 20),
+                 the values of ``siftmi_match_fit`` per segment.
+        """
+        blocks = int(blocks)
+        if blocks < 0 or blocks > 1024:
+            raise ValueError("blocks must be 0 .. 1024, not %d" % blocks)
+        args, S, n_pairs, pc, hold = self._estimate_batch_args(kp1, counts1, kp2, counts2, pairs, pair_counts, mask)
+        work = int(numpy.minimum(256, -(-pc // 256)).sum()) if blocks == 0 else blocks * int((pc > 0).sum())
+        if work > self.BATCH_MAX_WORK:
+            raise ValueError("%d workgroups in all: more than %d" % (work, self.BATCH_MAX_WORK))
+        raw = numpy.empty((S, 20), numpy.float64)
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_fit_batch(*args, blocks, raw.ctypes.data, C.byref(ms)))
+            if self.profile:
+                from .plan import StageEvent
+                self.events.append(("fit_batch", StageEvent(ms.value)))      # device time, first kernel to last
+        ok = raw[:, 0] == self.FIT_OK
+        models = numpy.where(ok[:, None], raw[:, 13:19], numpy.nan)
+        with numpy.errstate(all="ignore"):
+            rms = numpy.where(ok, numpy.sqrt(raw[:, 19] / raw[:, 1]), numpy.nan)
+        result = (models, rms, raw[:, 1].astype(numpy.int64))
+        return result + (raw,) if return_moments else result
+
+    def shift_batch(self, kp1, counts1, kp2, counts2, pairs, pair_counts, mask=None, tol=None, return_ranks=False):
+        """``shift(kp1_s, kp2_s, pairs_s, mask_s, tol)`` for the S segments of a ``match_batch`` in one call: one launch and one
+        synchronisation, every result bit for bit that of the single call (extension).  Arguments as
+        for ``fit_batch``; a median does not depend on the launch shape, so there is no ``blocks``.
+
+        :param tol: None, or a distance in pixels >= 0 (``inf`` is allowed): the result gains the keep mask, every row tested
+                    against the medians of its own segment, and the kept pairs per segment
+        :return: ``(shifts, n)``: float32 (S, 2) ``(dx, dy)`` with NaN rows where no pair is usable, and int64 (S,).  With ``tol``
+                 two more items: bool (M,) and int64 (S,); with ``return_ranks`` a last item, float32 (S, 6), the values of
+                 ``siftmi_match_shift`` per segment.
+        """
+        if tol is not None and not float(tol) >= 0.0:
+            raise ValueError("tol must be >= 0 (inf is allowed), not %r" % (tol,))
+        args, S, n_pairs, pc, hold = self._estimate_batch_args(kp1, counts1, kp2, counts2, pairs, pair_counts, mask)
+        raw = numpy.empty((S, 6), numpy.float32)
+        counts = numpy.zeros((S, 2), numpy.int64)
+        kept = numpy.zeros(n_pairs, numpy.uint8) if tol is not None else None
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_shift_batch(*args, C.c_float(0.0 if tol is None else tol),
+                                                           kept.ctypes.data if tol is not None else None, raw.ctypes.data,
+                                                           counts.ctypes.data, C.byref(ms)))
+            if self.profile:
+                from .plan import StageEvent
+                self.events.append(("shift_batch", StageEvent(ms.value)))    # device time of the kernel
+        result = (raw[:, :2].copy(), counts[:, 0].copy())
+        if tol is not None:
+            result += (kept.view(numpy.bool_), counts[:, 1].copy())
+        return result + (raw,) if return_ranks else result
+
     def _records(self, kp):
         if isinstance(kp, numpy.ndarray):
             arr = numpy.ascontiguousarray(kp)
