@@ -443,6 +443,39 @@ int siftmi_match_shift_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int6
                              const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device, const int64_t *pair_counts,
                              const uint8_t *mask, int32_t mask_is_device, float tol, uint8_t *keep, float *out, int64_t *counts,
                              double *kernel_ms);
+/* siftmi_match_consensus for every segment of a batch in one set of launches and one stream synchronisation (extension; DESIGN.md
+ * section 7 row 14, restated by tests/consensus_batch_ref.py).  The lists, n_segments, counts1 (NULL: one shared first list), counts2,
+ * pairs and pair_counts, and the gather rule -- an index outside its own segment's list gives four NaN, a record of a neighbouring
+ * segment is never read -- are siftmi_match_fit_batch's; n_hyp, tol and seed are siftmi_match_consensus's and hold for every segment.
+ * Segment s samples its triples mod pair_counts[s] with the row's position inside the segment as the pair index, and its mask rows,
+ * model, winner, votes and the rows of the two test hooks are bit for bit those of siftmi_match_consensus on the segment's own lists
+ * and pairs.  A segment with fewer than three pairs, or with no triple with |det| >= 1, has no winner: winner -1, 0 votes, a NaN
+ * model, its mask rows zero.  When no segment has three pairs (n_segments == 0 included) nothing is launched, *kernel_ms = 0, the
+ * mask is zeroed where it lies and every per-segment result is filled on the host.  Lists and pairs are used where they lie; host
+ * ones are staged.  One stream synchronisation per call, one copy back for the per-segment results and one for the mask only when
+ * it is a host mask.
+ * SIFTMI_EINVAL, nothing launched, nothing written: siftmi_match_fit_batch's (a null matcher, n_segments outside 0 .. 65 535, a
+ * negative count, a count above 2^31 - 1, counts that do not add up to n1 / n2, pair_counts that do not add up to n_pairs, a null
+ * list, pairs, counts2 or pair_counts where it is needed), n_hyp outside 1..2^20, tol not finite or not > 0, a null mask with a
+ * pair, null models, winners or winner_votes with a segment, (segments of three pairs or more) * n_hyp above 2^22 (their models,
+ * votes and flags live in the matcher's buffers, about 120 MB at the limit), more than 2^20 tiles in all (a tile: up to 1024 rows
+ * of one segment).
+ *   mask          n_pairs bytes aligned with the rows of `pairs`, every byte written: host, or device (mask_is_device: written where
+ *                 it lies, it goes into siftmi_match_fit_batch / siftmi_match_shift_batch as it is and no mask comes back)
+ *   models        host, n_segments * 6 floats (a, b, c, d, e, f); NaN where the segment has no winner
+ *   winners       host, n_segments: index of the winning map, -1: none      winner_votes  host, n_segments: its votes, 0 without
+ *   votes_all     optional, host, n_segments * n_hyp (test hook)            models_all    optional, host, n_segments * n_hyp * 6,
+ *                 void rows all NaN; a segment with fewer than three pairs: 0 / NaN, as the single call fills them (test hook)
+ *   kernel_ms     optional: hipEvent time of the vote kernel alone */
+int siftmi_match_consensus_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                                 const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                                 const int64_t *counts1, const int64_t *counts2,
+                                 const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device, const int64_t *pair_counts,
+                                 int32_t n_hyp, float tol, uint32_t seed,
+                                 uint8_t *mask, int32_t mask_is_device,
+                                 float *models, int32_t *winners, int32_t *winner_votes,
+                                 int32_t *votes_all, float *models_all,
+                                 double *kernel_ms);
 int siftmi_match_last_kernel_ms(const siftmi_matcher *plan, float *ms);
 /* profile != 0 at creation: device time in ms of the last call's stages, in the order of the events the reference
  * appends under profile=True (sift-src/match.py:226-263): ms4[0] "copy H->D KP_1", [1] "copy H->D KP_2", [2] "matching",

@@ -109,6 +109,10 @@ _SIGNATURES = {
     "siftmi_match_shift_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "siftmi_match_consensus_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
+                                               C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.POINTER(C.c_double)]),
     "siftmi_match_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "siftmi_match_last_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "siftmi_match_destroy": (C.c_int, [C.c_void_p]),

@@ -54,11 +54,9 @@ __global__ __launch_bounds__(256) void consensus_gather_kernel(const uint8_t *__
     pts[j] = v;
 }
 
-// one lane per hypothesis; also clears votes[h]
-__global__ __launch_bounds__(256) void consensus_solve_kernel(const float4 *__restrict__ pts, uint32_t M, int H, uint32_t seed,
-                                                              float *__restrict__ models, uint8_t *__restrict__ valid, int *__restrict__ votes) {
-    const int h = blockIdx.x * 256 + threadIdx.x;
-    if (h >= H) return;
+// hypothesis h of the M matches at pts: the sample and the binary64 solve of the contract, in the order written.  out: the six
+// coefficients as f32, all NaN when the triple is void; returns "not void".  Shared with k_consensus_batch.hpp
+__device__ __forceinline__ bool consensus_solve(const float4 *__restrict__ pts, uint32_t M, int h, uint32_t seed, float out[6]) {
     const uint32_t base = 3u * (uint32_t)h;
     const float4 m0 = pts[consensus_mix(seed + 0x9E3779B9u * (base + 1u)) % M];
     const float4 m1 = pts[consensus_mix(seed + 0x9E3779B9u * (base + 2u)) % M];
@@ -67,7 +65,8 @@ __global__ __launch_bounds__(256) void consensus_solve_kernel(const float4 *__re
     const double ux = (double)m1.x - x0, uy = (double)m1.y - y0, vx = (double)m2.x - x0, vy = (double)m2.y - y0;
     const double det = ux * vy - vx * uy;
     const float nan = __int_as_float(0x7fc00000);
-    float out[6] = {nan, nan, nan, nan, nan, nan};
+#pragma unroll
+    for (int k = 0; k < 6; k++) out[k] = nan;
     const bool ok = fabs(det) >= 1.0;
     if (ok) {
         const double px = (double)m1.z - x1, qx = (double)m2.z - x1, py = (double)m1.w - y1, qy = (double)m2.w - y1;
@@ -77,6 +76,16 @@ __global__ __launch_bounds__(256) void consensus_solve_kernel(const float4 *__re
         const double f = y1 - (d * x0 + e * y0);
         out[0] = (float)a; out[1] = (float)b; out[2] = (float)c; out[3] = (float)d; out[4] = (float)e; out[5] = (float)f;
     }
+    return ok;
+}
+
+// one lane per hypothesis; also clears votes[h]
+__global__ __launch_bounds__(256) void consensus_solve_kernel(const float4 *__restrict__ pts, uint32_t M, int H, uint32_t seed,
+                                                              float *__restrict__ models, uint8_t *__restrict__ valid, int *__restrict__ votes) {
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= H) return;
+    float out[6];
+    const bool ok = consensus_solve(pts, M, h, seed, out);
 #pragma unroll
     for (int k = 0; k < 6; k++) models[(size_t)h * 6 + k] = out[k];
     valid[h] = ok ? 1 : 0;
@@ -115,9 +124,10 @@ __global__ __launch_bounds__(SIFT_CONS_THREADS) void consensus_vote_kernel(const
     }
 }
 
-// one workgroup: maximum of (votes << 32 | ~h) over the non-void hypotheses = most votes, smallest h among equals
-__global__ __launch_bounds__(256) void consensus_select_kernel(const int *__restrict__ votes, const uint8_t *__restrict__ valid,
-                                                               const float *__restrict__ models, int H, ConsensusResult *__restrict__ result) {
+// one workgroup of 256 lanes: maximum of (votes << 32 | ~h) over the non-void hypotheses = most votes, smallest h among equals.
+// Shared with k_consensus_batch.hpp
+__device__ __forceinline__ void consensus_select(const int *__restrict__ votes, const uint8_t *__restrict__ valid,
+                                                 const float *__restrict__ models, int H, ConsensusResult *__restrict__ result) {
     __shared__ unsigned long long best[256];
     unsigned long long key = 0;                                   // 0: nothing (a real key has ~h != 0 in its lower half)
     for (int h = threadIdx.x; h < H; h += 256)
@@ -142,6 +152,11 @@ __global__ __launch_bounds__(256) void consensus_select_kernel(const int *__rest
         }
         *result = r;
     }
+}
+
+__global__ __launch_bounds__(256) void consensus_select_kernel(const int *__restrict__ votes, const uint8_t *__restrict__ valid,
+                                                               const float *__restrict__ models, int H, ConsensusResult *__restrict__ result) {
+    consensus_select(votes, valid, models, H, result);
 }
 
 __global__ __launch_bounds__(256) void consensus_mask_kernel(const float4 *__restrict__ pts, int M, const ConsensusResult *__restrict__ result,

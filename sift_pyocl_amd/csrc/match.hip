@@ -1,5 +1,5 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp), their exact median displacement (k_shift.hpp), the matcher over a batch of segment pairs (k_match_batch.hpp) and the fit and the median of every segment of such a batch at once (k_estimate_batch.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp), their exact median displacement (k_shift.hpp), the matcher over a batch of segment pairs (k_match_batch.hpp) the fit and the median of every segment of such a batch at once (k_estimate_batch.hpp) and the consensus filter over every segment at once (k_consensus_batch.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -16,6 +16,7 @@
 #include "k_shift.hpp"
 #include "k_match_batch.hpp"
 #include "k_estimate_batch.hpp"
+#include "k_consensus_batch.hpp"
 
 using namespace siftk;
 
@@ -91,6 +92,8 @@ struct siftmi_matcher {
     int64_t cap_eb_host = 0, cap_eb_tab = 0, cap_eb_res = 0;
     double *eb_f64 = nullptr;
     int64_t cap_eb_f64 = 0;
+    // segmented consensus (siftmi_match_consensus_batch): its table and the segments' results use eb_host, eb_tab and eb_res, the
+    // hypotheses of all active segments c_models, c_valid and c_votes, a host mask comes back through c_mask
 };
 
 namespace {
@@ -1205,6 +1208,144 @@ int siftmi_match_shift_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int6
     memcpy(counts, res, (size_t)cnt_bytes);
     memcpy(out, res + cnt_bytes, (size_t)(res_bytes - cnt_bytes));
     for (int s = 0; s < S; s++) if (pair_counts[s] == 0) empty_row(s);      // no workgroup wrote these
+    return SIFTMI_OK;
+}
+
+// The consensus filter over every segment of a batch at once (k_consensus_batch.hpp; the contract is DESIGN.md section 7 row 14)
+namespace {
+inline int64_t cb_tiles(int64_t rows) { return (rows + SIFT_CONS_TILE - 1) / SIFT_CONS_TILE; }
+// The table, segments in order: `tiles` gets the tiles of every segment, `segs` one entry per active segment (three pairs or more)
+void cb_fill(const EbBatch &a, CbWork *tiles, CbWork *segs) {
+    int64_t off1 = 0, off2 = 0, row0 = 0, t = 0;
+    int act = 0;
+    for (int s = 0; s < a.S; s++) {
+        const int64_t rows = a.pair_counts[s], n1 = a.counts1 ? a.counts1[s] : a.n1, n2 = a.counts2[s];
+        CbWork w = {s, rows >= 3 ? act : -1, (int)row0, (int)rows, (int)off1, (int)n1, (int)off2, (int)n2};
+        if (rows >= 3) segs[act++] = w;
+        for (int64_t r = 0; r < rows; r += SIFT_CONS_TILE) {
+            w.row0 = (int)(row0 + r); w.rows = (int)(rows - r < SIFT_CONS_TILE ? rows - r : SIFT_CONS_TILE);
+            tiles[t++] = w;
+        }
+        row0 += rows; off2 += n2;
+        if (a.counts1) off1 += n1;
+    }
+}
+
+void launch_cb_gather(hipStream_t st, int n_tiles, const uint8_t *d1, const uint8_t *d2, const int2 *dp, const CbWork *tiles, float4 *pts) {
+    hipLaunchKernelGGL(cb_gather_kernel, dim3((unsigned)n_tiles), dim3(SIFT_CONS_THREADS), 0, st, d1, d2, dp, tiles, pts);
+}
+void launch_cb_solve(hipStream_t st, int n_active, const float4 *pts, const CbWork *segs, int H, uint32_t seed, float *models, uint8_t *valid,
+                     int *votes) {
+    hipLaunchKernelGGL(cb_solve_kernel, dim3((unsigned)((H + 255) / 256), (unsigned)n_active), dim3(256), 0, st, pts, segs, H, seed, models,
+                       valid, votes);
+}
+// siftmi_match_consensus's vote grid with all tiles of the batch in place of one list's: about eight workgroups per CU, a chunk at
+// most the kernel's LDS counters and at least 16 hypotheses.  x: up to 2^20 tiles; y: at most max(2048, H / 512) = 2048 chunks
+void launch_cb_vote(hipStream_t st, int n_tiles, const float4 *pts, const CbWork *tiles, const float *models, int H, float tol2, int *votes) {
+    int chunks = (2048 + n_tiles - 1) / n_tiles;
+    const int min_chunks = (H + SIFT_CONS_HMAX - 1) / SIFT_CONS_HMAX, max_chunks = (H + 15) / 16;
+    if (chunks > max_chunks) chunks = max_chunks;
+    if (chunks < min_chunks) chunks = min_chunks;
+    const int h_chunk = (H + chunks - 1) / chunks;
+    chunks = (H + h_chunk - 1) / h_chunk;
+    hipLaunchKernelGGL(cb_vote_kernel, dim3((unsigned)n_tiles, (unsigned)chunks), dim3(SIFT_CONS_THREADS), 0, st, pts, tiles, models, H, h_chunk,
+                       tol2, votes);
+}
+void launch_cb_select(hipStream_t st, int n_active, const int *votes, const uint8_t *valid, const float *models, int H, ConsensusResult *results) {
+    hipLaunchKernelGGL(cb_select_kernel, dim3((unsigned)n_active), dim3(256), 0, st, votes, valid, models, H, results);
+}
+void launch_cb_mask(hipStream_t st, int n_tiles, const float4 *pts, const CbWork *tiles, const ConsensusResult *results, float tol2, uint8_t *mask) {
+    hipLaunchKernelGGL(cb_mask_kernel, dim3((unsigned)n_tiles), dim3(SIFT_CONS_THREADS), 0, st, pts, tiles, results, tol2, mask);
+}
+}  // namespace
+
+int siftmi_match_consensus_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                                 const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                                 const int64_t *counts1, const int64_t *counts2,
+                                 const int32_t *pairs, int64_t n_pairs, int32_t pairs_is_device, const int64_t *pair_counts,
+                                 int32_t n_hyp, float tol, uint32_t seed, uint8_t *mask, int32_t mask_is_device,
+                                 float *models, int32_t *winners, int32_t *winner_votes, int32_t *votes_all, float *models_all,
+                                 double *kernel_ms) {
+    const EbBatch a = {kp1, n1, kp1_is_device, kp2, n2, kp2_is_device, n_segments, counts1, counts2, pairs, n_pairs, pairs_is_device,
+                       pair_counts, nullptr, 0};
+    int rc;
+    if ((rc = eb_validate(m, a))) return rc;
+    const int S = n_segments, H = n_hyp;
+    if (n_hyp < 1 || n_hyp > (1 << 20)) return fail(SIFTMI_EINVAL, "n_hyp %d outside 1..2^20", n_hyp);
+    if (!std::isfinite(tol) || !(tol > 0.f)) return fail(SIFTMI_EINVAL, "tol must be finite and > 0");
+    if (n_pairs > 0 && !mask) return fail(SIFTMI_EINVAL, "null mask with %lld pairs", (long long)n_pairs);
+    if (S > 0 && (!models || !winners || !winner_votes)) return fail(SIFTMI_EINVAL, "null argument");
+    int64_t T = 0, A = 0;
+    for (int s = 0; s < S; s++) { T += cb_tiles(pair_counts[s]); A += pair_counts[s] >= 3; }
+    if (A * H > SIFT_CB_MAX_HYP) return fail(SIFTMI_EINVAL, "%lld segments of three pairs or more x %d hypotheses: more than %d", (long long)A, H, SIFT_CB_MAX_HYP);
+    if (T > SIFT_CB_MAX_TILES) return fail(SIFTMI_EINVAL, "%lld tiles in all: more than %d", (long long)T, SIFT_CB_MAX_TILES);
+    HIPCHK(hipSetDevice(m->device));
+    if (kernel_ms) *kernel_ms = 0.0;
+    // what a segment without a winner gets; the active segments' rows are replaced below
+    for (int s = 0; s < S; s++) { winners[s] = -1; winner_votes[s] = 0; }
+    for (int64_t i = 0; i < (int64_t)S * 6; i++) models[i] = std::nanf("");
+    if (votes_all) memset(votes_all, 0, sizeof(int32_t) * (size_t)S * (size_t)H);
+    if (models_all) for (int64_t i = 0; i < (int64_t)S * H * 6; i++) models_all[i] = std::nanf("");
+    if (A == 0) {           // every triple of every segment repeats an index: nothing is launched, the mask is all zero
+        if (n_pairs > 0 && mask_is_device) {
+            HIPCHK(hipDeviceSynchronize());
+            HIPCHK(hipMemsetAsync(mask, 0, (size_t)n_pairs, m->stream));
+            HIPCHK(hipStreamSynchronize(m->stream));
+        } else if (n_pairs > 0) {
+            memset(mask, 0, (size_t)n_pairs);
+        }
+        return SIFTMI_OK;
+    }
+    // the table, one upload: the tiles' entries, then one entry per active segment; behind them, on the host, the segments' results
+    const int64_t o_segs = T * (int64_t)sizeof(CbWork), tab_bytes = o_segs + A * (int64_t)sizeof(CbWork),
+                  res_bytes = A * (int64_t)sizeof(ConsensusResult);
+    if ((rc = ensure_pinned(&m->eb_host, &m->cap_eb_host, tab_bytes + res_bytes)) ||
+        (rc = ensure((void **)&m->eb_tab, &m->cap_eb_tab, tab_bytes, 1)) ||
+        (rc = ensure((void **)&m->eb_res, &m->cap_eb_res, res_bytes, 1)) ||
+        (rc = ensure((void **)&m->c_pts, &m->cap_c_pts, n_pairs, sizeof(float4))) ||
+        (rc = ensure((void **)&m->c_valid, &m->cap_c_valid, A * H, 1)) ||
+        (rc = ensure((void **)&m->c_models, &m->cap_c_models, A * H * 6, sizeof(float))) ||
+        (rc = ensure((void **)&m->c_votes, &m->cap_c_votes, A * H, sizeof(int)))) return rc;
+    if (!mask_is_device && (rc = ensure((void **)&m->c_mask, &m->cap_c_mask, n_pairs, 1))) return rc;
+    cb_fill(a, (CbWork *)m->eb_host, (CbWork *)(m->eb_host + o_segs));
+    if (mask_is_device && !(kp1_is_device || kp2_is_device || pairs_is_device)) HIPCHK(hipDeviceSynchronize());   // eb_stage: the inputs
+    const uint8_t *d1, *d2, *dm;
+    const int2 *dp;
+    if ((rc = eb_stage(m, a, &d1, &d2, &dp, &dm))) return rc;
+    HIPCHK(hipMemcpyAsync(m->eb_tab, m->eb_host, (size_t)tab_bytes, hipMemcpyHostToDevice, m->stream));
+    const CbWork *tiles = (const CbWork *)m->eb_tab, *segs = (const CbWork *)(m->eb_tab + o_segs);
+    ConsensusResult *results = (ConsensusResult *)m->eb_res, *res = (ConsensusResult *)(m->eb_host + tab_bytes);
+    uint8_t *dmask = mask_is_device ? mask : m->c_mask;
+    const float tol2 = tol * tol;
+    launch_cb_gather(m->stream, (int)T, d1, d2, dp, tiles, m->c_pts);
+    launch_cb_solve(m->stream, (int)A, (const float4 *)m->c_pts, segs, H, seed, m->c_models, m->c_valid, m->c_votes);
+    hipEventRecord(m->ec_a, m->stream);
+    launch_cb_vote(m->stream, (int)T, (const float4 *)m->c_pts, tiles, (const float *)m->c_models, H, tol2, m->c_votes);
+    hipEventRecord(m->ec_b, m->stream);
+    launch_cb_select(m->stream, (int)A, (const int *)m->c_votes, (const uint8_t *)m->c_valid, (const float *)m->c_models, H, results);
+    launch_cb_mask(m->stream, (int)T, (const float4 *)m->c_pts, tiles, (const ConsensusResult *)results, tol2, dmask);
+    HIPCHK(hipMemcpyAsync(res, results, (size_t)res_bytes, hipMemcpyDeviceToHost, m->stream));
+    if (!mask_is_device) HIPCHK(hipMemcpyAsync(mask, m->c_mask, (size_t)n_pairs, hipMemcpyDeviceToHost, m->stream));
+    if (votes_all || models_all) {      // test hooks: the rows of active segment `act` go to segment s
+        int64_t act = 0;
+        for (int s = 0; s < S; s++) {
+            if (pair_counts[s] < 3) continue;
+            if (votes_all) HIPCHK(hipMemcpyAsync(votes_all + (size_t)s * H, m->c_votes + act * H, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, m->stream));
+            if (models_all) HIPCHK(hipMemcpyAsync(models_all + (size_t)s * H * 6, m->c_models + act * H * 6, sizeof(float) * 6 * (size_t)H,
+                                                  hipMemcpyDeviceToHost, m->stream));
+            act++;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, m->ec_a, m->ec_b); *kernel_ms = ms; }
+    int64_t act = 0;
+    for (int s = 0; s < S; s++) {
+        if (pair_counts[s] < 3) continue;
+        const ConsensusResult &r = res[act++];
+        winners[s] = r.winner; winner_votes[s] = r.votes;
+        if (r.winner >= 0) memcpy(models + (size_t)s * 6, r.model, sizeof r.model);
+    }
     return SIFTMI_OK;
 }
 

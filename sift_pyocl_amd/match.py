@@ -545,6 +545,61 @@ class MatchPlan(object):
             result += (kept.view(numpy.bool_), counts[:, 1].copy())
         return result + (raw,) if return_ranks else result
 
+    BATCH_MAX_HYP = 1 << 22
+
+    def consensus_batch(self, kp1, counts1, kp2, counts2, pairs, pair_counts, n_hyp=2048, tol=3.0, seed=0, return_votes=False,
+                        out="host"):
+        """``consensus(kp1_s, kp2_s, pairs_s, n_hyp, tol, seed)`` for the S segments of a ``match_batch`` in one call: one set of
+        launches and one synchronisation, every result bit for bit that of the single call (extension).
+        The first six arguments are ``fit_batch``'s; ``n_hyp``, ``tol`` and ``seed`` are ``consensus``'s and hold for every segment.
+        An index outside its segment's own list never votes; a record of a neighbouring segment is never read.
+
+        :param kp1, counts1, kp2, counts2: as for ``match_batch`` (``counts1=None``: one shared first list)
+        :param pairs: (M, 2) int32 indices local to the segment, a numpy array or a device tensor
+        :param pair_counts: S non-negative ints that add up to M
+        :param out: ``"host"``: ``mask`` is a numpy bool array; ``"device"``: a torch uint8 tensor on the plan's device that goes
+                    into ``fit_batch(mask=)`` / ``shift_batch(mask=)`` as it is, and no mask is copied back
+        :return: ``(mask, models, votes)``: (M,) aligned with the rows of ``pairs``, float32 (S, 6) with NaN rows where a segment has
+                 no winner (fewer than three pairs, no usable triple: its mask rows are zero) and int32 (S,) votes of the winners;
+                 with ``return_votes`` a fourth item ``(winners, votes_all, models_all)``: int32 (S,) with -1 for none, int32
+                 (S, n_hyp), float32 (S, n_hyp, 6) with unusable triples as NaN rows
+        """
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        n_hyp, tol = int(n_hyp), float(tol)
+        if n_hyp < 1 or n_hyp > (1 << 20):
+            raise ValueError("n_hyp must be 1 .. 2**20, not %d" % n_hyp)
+        if not (abs(tol) <= float(numpy.finfo(numpy.float32).max) and tol > 0.0):      # finite as the float32 the library gets
+            raise ValueError("tol must be finite and > 0, not %r" % (tol,))
+        args, S, n_pairs, pc, hold = self._estimate_batch_args(kp1, counts1, kp2, counts2, pairs, pair_counts, None)
+        if int((pc >= 3).sum()) * n_hyp > self.BATCH_MAX_HYP:
+            raise ValueError("%d segments of three pairs or more x %d hypotheses: more than %d" % ((pc >= 3).sum(), n_hyp, self.BATCH_MAX_HYP))
+        tiles = int((-(-pc // 1024)).sum())
+        if tiles > self.BATCH_MAX_WORK:
+            raise ValueError("%d tiles in all: more than %d" % (tiles, self.BATCH_MAX_WORK))
+        if out == "device":
+            import torch
+            mask = torch.empty(n_pairs, dtype=torch.uint8, device=torch.device("cuda", self.device))
+            pmask = mask.data_ptr()
+        else:
+            mask = numpy.empty(n_pairs, numpy.uint8)
+            pmask = mask.ctypes.data
+        models = numpy.empty((S, 6), numpy.float32)
+        winners, votes = numpy.empty(S, numpy.int32), numpy.empty(S, numpy.int32)
+        votes_all = numpy.empty((S, n_hyp), numpy.int32) if return_votes else None
+        models_all = numpy.empty((S, n_hyp, 6), numpy.float32) if return_votes else None
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_consensus_batch(
+                *args[:-2], n_hyp, C.c_float(tol), int(seed) & 0xFFFFFFFF, pmask if n_pairs else None, int(out == "device"),
+                models.ctypes.data, winners.ctypes.data, votes.ctypes.data, votes_all.ctypes.data if return_votes else None,
+                models_all.ctypes.data if return_votes else None, C.byref(ms)))
+            if self.profile:
+                from .plan import StageEvent
+                self.events.append(("consensus_batch", StageEvent(ms.value)))    # device time of the vote kernel
+        result = (mask if out == "device" else mask.view(numpy.bool_), models, votes)
+        return result + ((winners, votes_all, models_all),) if return_votes else result
+
     def _records(self, kp):
         if isinstance(kp, numpy.ndarray):
             arr = numpy.ascontiguousarray(kp)
