@@ -152,11 +152,16 @@ int siftmi_plan_records_device(const siftmi_plan *plan, const siftmi_keypoint **
  *                  folded in).  The fused detect-and-refine launch keeps no candidate list: its octaves read 0 here.
  *   c_scale        [n_octaves][3] candidates of the octave per detection scale 1, 2, 3, as the refinement read them
  *   n_octaves      octaves the two arrays have room for (>= the plan's)
- * SIFTMI_EINVAL, nothing written: a null plan or buffer, a buffer that is too small, an octave outside 0..n_octaves-1, a plan
- * that has not finished a call (none yet, or the last one failed). */
+ * siftmi_plan_tail_candidates  copies the candidate list octave_tail_kernel kept for `octave` -- min(candidates[octave], 3 * 4096)
+ *                          entries (value, row, col, scale) of four floats, in no particular order -- to the host buffer `out` of
+ *                          `capacity` floats and returns their number in *count.  Only that launch writes the list; an octave
+ *                          below `tail_first` of the run that produced the result has none (also after a tail time-out).
+ * SIFTMI_EINVAL, nothing written: a null plan or buffer, a buffer that is too small, an octave outside 0..n_octaves-1 (tail
+ * candidates: outside tail_first..n_octaves-1), a plan that has not finished a call (none yet, or the last one failed). */
 int siftmi_plan_planes(siftmi_plan *plan, int32_t octave, float *out, int64_t capacity, int32_t *width, int32_t *height);
 int siftmi_plan_last_counts(const siftmi_plan *plan, int32_t *tail_first, int32_t *candidates, int32_t *c_scale,
                             int32_t n_octaves);
+int siftmi_plan_tail_candidates(const siftmi_plan *plan, int32_t octave, float *out, int64_t capacity, int64_t *count);
 /* Affine warp with bilinear interpolation of an image of the plan's shape -- the `transform` / `transform_RGB`
  * kernels (openCL/transform.cl:22, :116) as LinearAlign.align launches them (sift-src/alignment.py:325-348).
  *   out[y][x] = bilinear(image, (ty, tx)),  ty = matrix[0]*y + matrix[1]*x + offset[0],

@@ -1623,6 +1623,29 @@ int siftmi_plan_last_counts(const siftmi_plan *p, int32_t *tail_first, int32_t *
     return SIFTMI_OK;
 }
 
+// The candidate list octave_tail_kernel kept for one of its octaves in the last finished call (see include/siftmi.h).  Nothing
+// is launched; p->tail_cand is written by that launch alone (launch_tail), workgroup k = octave - tail_first at k * tail_cand_cap.
+int siftmi_plan_tail_candidates(const siftmi_plan *p, int32_t octave, float *out, int64_t capacity, int64_t *count) {
+    if (!p) return fail(SIFTMI_EINVAL, "null plan");
+    if (!out || !count) return fail(SIFTMI_EINVAL, "null output");
+    if (!p->last_valid || p->in_flight) return fail(SIFTMI_EINVAL, "the plan has not finished a call: there are no candidates to read");
+    if (octave < p->last_tail_first || octave >= p->n_oct || octave >= SIFT_MAX_OCTAVES || octave - p->last_tail_first >= SIFT_TAIL_MAX_OCT)
+        return fail(SIFTMI_EINVAL, "octave %d is not one of the tail launch's (%d..%d) in the run that produced the result", octave,
+                    p->last_tail_first, p->n_oct - 1);
+    const int64_t n = std::max(0, std::min(p->last_n_cand[octave], p->tail_cand_cap));
+    if (capacity < 4 * n) return fail(SIFTMI_EINVAL, "buffer of %lld floats, octave %d needs 4 * %lld", (long long)capacity, octave, (long long)n);
+    if (n > 0) {
+        HIPCHK(hipSetDevice(p->device));
+        for (hipStream_t s : {p->stream2, p->stream3})
+            if (s) HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpyAsync(out, p->tail_cand + (size_t)(octave - p->last_tail_first) * p->tail_cand_cap, (size_t)n * sizeof(float4),
+                              hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+    }
+    *count = n;
+    return SIFTMI_OK;
+}
+
 // ---- batched, pipelined keypoints --------------------------------------------------------
 // `lanes` independent plans (own planes, lists and streams) take the images round-robin.  Everything is enqueued
 // without waiting; a lane is only waited for when it is about to be reused, and its records are then parked in a

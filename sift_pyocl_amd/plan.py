@@ -415,6 +415,20 @@ class SiftPlan(object):
             _lib.check(L.siftmi_plan_last_counts(self._handle, C.byref(first), cand.ctypes.data, cs.ctypes.data, n))
         return dict(tail_first=int(first.value), candidates=[int(v) for v in cand[:n_oct.value]], c_scale=cs[:n_oct.value].copy())
 
+    def tail_candidates(self, octave):
+        """The candidate list the one-launch form of the small octaves kept for `octave` in the last finished keypoints()
+        call: (n, 4) float32 rows (value, row, col, scale) in no particular order.  Nothing is launched; an octave that
+        launch did not take (below ``last_counts()["tail_first"]``) raises RuntimeError."""
+        octave = int(octave)
+        counts = self.last_counts()
+        if not counts["tail_first"] <= octave < len(counts["candidates"]):
+            raise RuntimeError("octave %d is not one of the tail launch's (%d..%d)" % (octave, counts["tail_first"], len(counts["candidates"]) - 1))
+        out = numpy.empty((max(0, counts["candidates"][octave]), 4), numpy.float32)
+        n = C.c_int64()
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_plan_tail_candidates(self._handle, octave, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value]
+
     def minmax(self):
         """(min, max) of the last processed image (buffers["min"], buffers["max"] in the reference)."""
         mn, mx = C.c_float(), C.c_float()

@@ -162,6 +162,29 @@ def wave_totals(cand, W, H):
     return total, strips
 
 
+def check_left_behind(plan, exp, what, tail_first, fused_refine=1):
+    """Everything a finished keypoints() call left behind on `plan` against an Expect-like `exp` (sizes, planes, c_scale): the
+    first tail octave, all six planes of every octave, the candidates per octave and scale, the candidates per octave wherever
+    detection keeps a list -- uint32 / integer equality.  Returns plan.last_counts()."""
+    counts = plan.last_counts()
+    n_oct = len(exp.sizes)
+    assert counts["tail_first"] == tail_first, "%s: the tail launch took octaves from %d on, not from %d (of %d)" % (
+        what, counts["tail_first"], tail_first, n_oct)
+    for o in range(n_oct):
+        bad = plane_mismatch(plan.planes(o), exp.planes[o], o)
+        assert bad is None, "%s: %s" % (what, bad)
+    assert counts["c_scale"].shape == (n_oct, 3)
+    assert np.array_equal(counts["c_scale"], exp.c_scale), "%s: candidates per octave and scale %r, oracle %r" % (
+        what, counts["c_scale"].tolist(), np.asarray(exp.c_scale).tolist())
+    # candidates per octave == the per-scale sum wherever detection keeps a candidate list (every tail octave does); the fused
+    # detect-and-refine launch keeps none and must leave its counter at 0 (listed_octaves)
+    listed = listed_octaves(exp.sizes, tail_first, fused_refine)
+    want = [int(exp.c_scale[o].sum()) if listed[o] else 0 for o in range(n_oct)]
+    assert counts["candidates"] == want, "%s: candidates per octave %r, expected %r (octaves with a list: %r)" % (
+        what, counts["candidates"], want, listed)
+    return counts
+
+
 def plane_mismatch(got, want, octave):
     """None, or the message of the first plane of an octave that differs bit for bit: octave, plane, the first differing (y, x),
     the number of differing samples."""

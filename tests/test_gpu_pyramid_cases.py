@@ -49,24 +49,10 @@ def check_call(plan, oracle, frame, opts=None, what="", tail_first=None, records
     what = "%s %s %r" % (frame.name, what, opts)
     exp = pc.expectations(oracle, frame)
     got = plan.keypoints(pc.image(frame))
-    counts = plan.last_counts()
-    n_oct = len(exp.sizes)
     if tail_first is None:
         tail_first = pc.tail_first(exp.sizes, tail=opts.get("tail", 1), tail_pixels=opts.get("tail_pixels", pc.TAIL_PIXELS))
-    assert counts["tail_first"] == tail_first, "%s: the tail launch took octaves from %d on, not from %d (of %d)" % (
-        what, counts["tail_first"], tail_first, n_oct)
-    for o in range(n_oct):
-        bad = pc.plane_mismatch(plan.planes(o), exp.planes[o], o)
-        assert bad is None, "%s: %s" % (what, bad)
-    assert counts["c_scale"].shape == (n_oct, 3)
-    assert np.array_equal(counts["c_scale"], exp.c_scale), "%s: candidates per octave and scale %r, oracle %r" % (
-        what, counts["c_scale"].tolist(), exp.c_scale.tolist())
-    # candidates per octave == the per-scale sum wherever detection keeps a candidate list (every tail octave does); the fused
-    # detect-and-refine launch keeps none and must leave its counter at 0 (pyramid_cases.listed_octaves)
-    listed = pc.listed_octaves(exp.sizes, tail_first, opts.get("fused_refine", 1))
-    want = [int(exp.c_scale[o].sum()) if listed[o] else 0 for o in range(n_oct)]
-    assert counts["candidates"] == want, "%s: candidates per octave %r, expected %r (octaves with a list: %r)" % (
-        what, counts["candidates"], want, listed)
+    # (the comparisons live in pyramid_cases.check_left_behind, shared with tests/test_gpu_tail_flush.py)
+    pc.check_left_behind(plan, exp, what, tail_first, opts.get("fused_refine", 1))
     if records:
         assert_same_keypoints(got, _records(oracle, frame), what)
     return got
