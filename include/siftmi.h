@@ -229,6 +229,31 @@ int siftmi_batch_keypoints_into(siftmi_batch *batch, const void *const *images, 
                                 int32_t images_are_device, siftmi_keypoint *const *host_outs, const int64_t *host_caps,
                                 int64_t *counts, int64_t *offsets, int64_t *total_parked, int32_t *overflow);
 int siftmi_batch_fetch(siftmi_batch *batch, siftmi_keypoint *out, int32_t out_is_device, int64_t first, int64_t count);
+/* The two ends of aligning a stack (the reference aligns frame by frame: LinearAlign.align, alignment.py:225-360).
+ * siftmi_batch_minmax     min and max of every frame of the last FINISHED siftmi_batch_keypoints[_into], in input order: each
+ *                         lane's values recorded under the frame's index as the lane retires, i.e. what
+ *                         siftmi_plan_get_minmax returns for the same frame, from the same kernel (RGB8 and typed frames
+ *                         included).  Either array may be null.  Launches nothing.  SIFTMI_EINVAL: a null handle, n_images not
+ *                         that batch's size, no batch finished yet (none run, or the last one failed).
+ * siftmi_batch_transform  siftmi_plan_transform for n frames of the batch's H x W in ONE launch (transform_batch_kernel /
+ *                         transform_rgb_batch_kernel, csrc/k_align_batch.hpp), one synchronisation and at most one copy each
+ *                         way besides the 40-byte-per-frame table: frame s of `out` is bit for bit what siftmi_plan_transform
+ *                         writes for (images[s], maps[s], fills[s], mode).  A map with a non-finite entry gives a plane of
+ *                         fills[s] wherever the entry reaches (an all-NaN map: the whole plane).
+ *   images       n pointers, all host or all device (images_are_device); host frames are staged in a buffer the batch owns
+ *                and grows, one copy per run of frames that lie back to back in host memory (a contiguous stack: one copy)
+ *   out          n x OH x OW (x 3) contiguous, host (staged in a buffer the batch owns and grows, one copy back) or device
+ *   maps         n x 6 floats: matrix[4] then offset[2] of each frame, as siftmi_plan_transform takes them
+ *   fills        n floats; RGB8: each in [0, 255], as for siftmi_plan_transform
+ *   kernel_ms    optional, hipEvent duration of the launch (0 when nothing is launched)
+ * Device pointers are ordered after the NULL stream as everywhere (conventions, above).  n_images == 0 or an empty output
+ * launches nothing and returns 0.  SIFTMI_EINVAL, nothing launched: a null handle, a null table or output with work to do, a
+ * null frame, channels other than 1 or 3, a negative shape or count, n_images > 65535, out_height > 262140. */
+int siftmi_batch_transform(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
+                           int32_t channels, void *out, int32_t out_is_device, int32_t out_width, int32_t out_height,
+                           const float *maps /* n x 6: matrix[4], offset[2] */, const float *fills /* n */,
+                           int32_t mode, double *kernel_ms);
+int siftmi_batch_minmax(const siftmi_batch *batch, float *mins, float *maxs, int32_t n_images);
 
 /* ---- MatchPlan -----------------------------------------------------------------------------
  * siftmi_match_create <- MatchPlan.__init__ (match.py:77-139)

@@ -403,6 +403,150 @@ class LinearAlign(object):
 
     __call__ = align
 
+    # ------------------------------------------------------------------ a whole stack in one pass
+    def _batch_plan(self, lanes=None):
+        """the ``BatchPlan`` of ``align_batch``, created on first use (and again when another number of lanes is asked for)"""
+        from .batch import BatchPlan
+        bp = getattr(self, "_batch", None)
+        if bp is None or (lanes is not None and int(lanes) != bp.lanes):
+            shape, dtype = (self.shape + (3,), numpy.uint8) if self.RGB else (self.shape, numpy.float32)
+            bp = BatchPlan(shape=shape, dtype=dtype, device=self.device, init_sigma=self.sift._init_sigma, lanes=lanes)
+            self._batch = bp
+        return bp
+
+    def _device_frames(self, images):
+        """The frames of ``align_batch`` as device tensors of the aligner's frame type.  Host frames are converted as ``align``
+        converts them and cross the link once, as one stack; device tensors are taken as they are."""
+        import torch
+        fshape = self.shape + ((3,) if self.RGB else ())
+        ndtype = numpy.uint8 if self.RGB else numpy.float32
+        tdtype = torch.uint8 if self.RGB else torch.float32
+        dev = torch.device("cuda", self.device)
+        if isinstance(images, numpy.ndarray) and images.ndim == len(fshape) + 1:
+            if tuple(images.shape[1:]) != fshape:
+                raise RuntimeError("the stack has frames of shape %s, the aligner takes %s" % (tuple(images.shape[1:]), fshape))
+            if images.shape[0] == 0:
+                return []
+            whole = torch.from_numpy(numpy.ascontiguousarray(images, ndtype)).to(dev)       # a host stack: one copy
+            return [whole[i] for i in range(whole.shape[0])]
+        if hasattr(images, "shape") and len(images.shape) == len(fshape) + 1:
+            images = [images[i] for i in range(int(images.shape[0]))]
+        else:
+            images = list(images)
+        on_dev = [bool(getattr(f, "is_cuda", False)) for f in images]
+        if any(on_dev) and not all(on_dev):
+            raise RuntimeError("the frames of a stack must be all host arrays or all device tensors")
+        for i, f in enumerate(images):
+            if tuple(f.shape) != fshape:
+                raise RuntimeError("frame %d has shape %s, the aligner takes %s" % (i, tuple(f.shape), fshape))
+        if images and all(on_dev):
+            for i, f in enumerate(images):
+                if f.dtype != tdtype:
+                    raise RuntimeError("device frame %d is %s, the aligner takes %s" % (i, f.dtype, tdtype))
+            return [f.contiguous() for f in images]
+        if not images:
+            return []
+        # separate host frames go straight into their plane of the device stack, one copy each: stacking them on the host first
+        # costs more than the copies (64 frames of 2048 x 2048: 140 ms for stack and upload against the link's 20 ms)
+        stack = torch.empty((len(images),) + fshape, dtype=tdtype, device=dev)
+        for i, f in enumerate(images):
+            host = f if hasattr(f, "numpy") else torch.from_numpy(numpy.ascontiguousarray(f, ndtype))      # the cast of align()
+            stack[i].copy_(host)
+        return [stack[i] for i in range(len(images))]
+
+    def align_batch(self, images, shift_only=False, robust=False, robust_tol=3.0, robust_hyp=2048, match_ratio=None, return_all=False,
+                    out="host", lanes=None):
+        """Align a stack of S frames on the reference image in one pass (extension): every stage runs
+        once for the whole stack, each with one synchronisation -- ``BatchPlan.keypoints_batch_device`` -> ``minmax_batch`` (the
+        fill values) -> ``MatchPlan.match_batch`` against the reference list -> ``consensus_batch`` under ``robust`` ->
+        ``fit_batch`` / ``shift_batch`` -> ``BatchPlan.transform_batch``.  Keypoints, pairs and masks never leave the device; a
+        host frame crosses the link once, into a device stack that both detection and the warp read.  Greyscale and RGB aligners,
+        ``extra`` and ``ROI`` as for ``align``.
+
+        Per frame the estimate is what ``align(estimate="device", median="device")`` computes, with one difference: a degenerate
+        (collinear) segment of 18 pairs or more takes the median shift here; ``align`` takes the host's minimum-norm fit.  A frame is
+        *affine* (mode 2) when ``fit_batch`` gives it a finite map from at least 18 pairs (never under ``shift_only``); any other
+        frame with a usable pair takes ``shift_batch``'s median displacement (mode 1); a frame without one (mode 0) is not
+        dropped as ``align`` returns None: its map is all NaN, its plane comes out as the frame's fill value, and a warning names it.
+        Under ``robust`` a frame without a winning map uses all its pairs, as ``align`` does.
+
+        Device memory beside the plans: ``S * (H * W + OH * OW)`` elements (the stack and the result); a stack that does not fit
+        is the caller's to slice.  ``relative``, ``double_check``, ``orsa``, ``max_shift`` and ``match_metric`` have no batch form.
+
+        :param images: S frames of the reference's shape: host arrays (converted as ``align`` converts them), device tensors of
+                       the frame type (float32, or uint8 for RGB), or one (S, H, W[, 3]) stack of either
+        :param shift_only: estimate translations only
+        :param robust, robust_tol, robust_hyp: as for ``align`` (``consensus_batch`` with seed 0)
+        :param match_ratio: None (``par.MatchRatio``) or the ratio of the matcher's test, as for ``match_batch``
+        :param return_all: return a dict of per-frame arrays instead of the stack: ``result``, ``matrix`` (S, 2, 2), ``offset``
+                       (S, 2), ``mode`` (S,) int8, ``n`` (pairs the estimate used), ``rms`` (``fit_batch``'s value where affine, NaN
+                       elsewhere), ``fill``, ``counts``, ``keypoint`` (list of recarrays), ``pairs`` (M, 2) with indices local to the
+                       frame, ``pair_counts``, and under ``robust`` ``inliers``, the bool (M,) mask over ``pairs`` that was used
+        :param out: ``"host"``: the stack is a numpy array; ``"device"``: a torch tensor on the aligner's device
+        :param lanes: lanes of the ``BatchPlan`` (created on first use); None: its default for the frame size
+        :return: the aligned stack (S, OH, OW[, 3]), or the dict
+        """
+        import torch
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        with self.sem:
+            bp = self._batch_plan(lanes)
+            frames = self._device_frames(images)
+            S = len(frames)
+            ref_list = self.ref_kp if self._ref_dev is None else self._ref_dev
+            counts, records = bp.keypoints_batch_device(frames)
+            fills = bp.minmax_batch()[0]
+            counts = numpy.asarray(counts, numpy.int64).reshape(S)
+            dev = torch.device("cuda", self.device)
+            if self.ref_kp.size and int(counts.sum()):
+                pairs, pc = self.match.match_batch(ref_list, None, records, counts, ratio=match_ratio, out="device")
+            else:
+                pairs, pc = torch.empty((0, 2), dtype=torch.int32, device=dev), numpy.zeros(S, numpy.int64)
+            starts = numpy.concatenate([[0], numpy.cumsum(pc)]).astype(numpy.int64)
+            lists = (ref_list, None, records, counts, pairs, pc)
+            matched = int(pc.sum()) > 0
+            mask = None
+            if robust and matched:
+                mask, winners = self.match.consensus_batch(*lists, n_hyp=robust_hyp, tol=robust_tol, seed=0, out="device")[:2]
+                for s in numpy.nonzero(numpy.isnan(winners).any(axis=1) & (pc > 0))[0]:
+                    logger.warning("No consensus among %s matches of frame %d: all of them are used" % (pc[s], s))
+                    mask[int(starts[s]):int(starts[s + 1])] = 1
+            matrix = numpy.full((S, 2, 2), numpy.nan, numpy.float32)
+            offset = numpy.full((S, 2), numpy.nan, numpy.float32)
+            mode = numpy.zeros(S, numpy.int8)
+            used = numpy.zeros(S, numpy.int64)
+            rms = numpy.full(S, numpy.nan, numpy.float64)
+            affine = numpy.zeros(S, bool)
+            if matched and not shift_only:
+                models, fit_rms, n_fit = self.match.fit_batch(*lists, mask=mask)
+                affine = numpy.isfinite(models).all(axis=1) & (n_fit >= MIN_MATCHES_AFFINE)
+                a, b, c, d, e, f = (models[affine, k] for k in range(6))
+                matrix[affine] = numpy.stack([e, d, b, a], axis=1).reshape(-1, 2, 2).astype(numpy.float32)
+                offset[affine] = numpy.stack([f, c], axis=1).astype(numpy.float32)
+                mode[affine], used[affine], rms[affine] = 2, n_fit[affine], fit_rms[affine]
+            if matched and (~affine & (pc > 0)).any():
+                moved, n_moved = self.match.shift_batch(*lists, mask=mask)
+                shifted = ~affine & (n_moved > 0)
+                matrix[shifted] = numpy.identity(2, dtype=numpy.float32)
+                offset[shifted] = moved[shifted][:, ::-1]                    # (dx, dy) -> the kernel's (y, x) order
+                mode[shifted], used[shifted] = 1, n_moved[shifted]
+            for s in numpy.nonzero(mode == 0)[0]:
+                logger.warning("No matching keypoints in frame %d: its plane is the fill value" % s)
+            result = bp.transform_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, out=out)
+            self.last_transform_ms = bp.last_transform_ms
+            if self.profile:
+                self.events.append(("transform_batch", StageEvent(bp.last_transform_ms)))
+            if not return_all:
+                return result
+            host = records.cpu().numpy()
+            ends = numpy.cumsum(counts) * 144
+            keypoint = [host[int(e - 144 * n):int(e)].copy().view(SiftPlan.dtype_kp).view(numpy.recarray) for e, n in zip(ends, counts)]
+            res = {"result": result, "matrix": matrix, "offset": offset, "mode": mode, "n": used, "rms": rms, "fill": fills,
+                   "counts": counts, "keypoint": keypoint, "pairs": pairs.cpu().numpy(), "pair_counts": pc}
+            if robust:
+                res["inliers"] = mask.cpu().numpy().astype(bool) if mask is not None else numpy.zeros(0, bool)
+            return res
+
     def log_profile(self):
         """Print the timing of every recorded device call (profile=True)"""
         if not self.profile:

@@ -40,6 +40,8 @@ class BatchPlan(SiftPlan):
             lanes = 2 if px == 0 or px > 2048 * 2048 else (16 if px > 600 * 600 else 8)
         self.lanes = int(lanes)
         self._records_per_frame = 4096.0
+        self._batch_frames = None            # frames of the last finished batch (minmax_batch)
+        self.last_transform_ms = 0.0
         self._light = kwargs.get("profile") == "light"
         if kwargs.get("profile") and not self._light:
             raise RuntimeError("BatchPlan only supports profile='light' (blur brackets); profile a SiftPlan for per-stage events")
@@ -124,6 +126,7 @@ class BatchPlan(SiftPlan):
         images = list(images)
         n = len(images)
         if n == 0:
+            self._batch_frames = 0
             return []
         with self._sem:
             L = _lib.lib()
@@ -133,6 +136,7 @@ class BatchPlan(SiftPlan):
             offsets = (C.c_int64 * n)()
             parked = C.c_int64(0)
             ovf = C.c_int32(0)
+            self._batch_frames = None
             # Records are delivered frame by frame into host arrays while the batch runs.  Their capacity is a guess (1.5x
             # the records per frame of the previous batch); a frame that does not fit stays parked on the device and is
             # fetched afterwards.  Many lanes of small frames: the host must keep feeding the lanes, so everything is
@@ -149,6 +153,7 @@ class BatchPlan(SiftPlan):
                     caps[i] = cap
             _lib.check(L.siftmi_batch_keypoints_into(self._handle, ptrs, n, code, is_dev, outs if direct else None,
                                                      caps if direct else None, counts, offsets, C.byref(parked), C.byref(ovf)))
+            self._batch_frames = n
             self.overflow = bool(ovf.value)
             if self.overflow:
                 logger.warning("Keypoint counter overflow: an octave of a frame needs more than %s entries, result cut to that per octave", self.kpsize)
@@ -176,6 +181,7 @@ class BatchPlan(SiftPlan):
         n = len(images)
         dev = torch.device("cuda", self.device)
         if n == 0:
+            self._batch_frames = 0
             return [], torch.empty(0, dtype=torch.uint8, device=dev)
         with self._sem:
             L = _lib.lib()
@@ -185,8 +191,10 @@ class BatchPlan(SiftPlan):
             offsets = (C.c_int64 * n)()
             parked = C.c_int64(0)
             ovf = C.c_int32(0)
+            self._batch_frames = None
             _lib.check(L.siftmi_batch_keypoints_into(self._handle, ptrs, n, code, is_dev, None, None, counts, offsets,
                                                      C.byref(parked), C.byref(ovf)))
+            self._batch_frames = n
             self.overflow = bool(ovf.value)
             out = torch.empty(max(1, parked.value) * RECORD_BYTES, dtype=torch.uint8, device=dev)
             if parked.value:
@@ -205,6 +213,118 @@ class BatchPlan(SiftPlan):
         return self.keypoints_batch([image])[0]
 
     __call__ = keypoints
+
+    def minmax_batch(self):
+        """``(mins, maxs)`` of the frames of the last finished ``keypoints_batch`` / ``keypoints_batch_device``, two float32
+        ``(S,)`` arrays in input order: for every frame the values ``SiftPlan.minmax()`` gives after ``keypoints(frame)``
+        (``siftmi_batch_minmax``; nothing is launched).  RuntimeError when no batch has finished."""
+        n = self._batch_frames
+        if n is None:
+            raise RuntimeError("no batch has finished on this plan")
+        mins, maxs = numpy.empty(n, numpy.float32), numpy.empty(n, numpy.float32)
+        if n:
+            with self._sem:
+                _lib.check(_lib.lib().siftmi_batch_minmax(self._handle, mins.ctypes.data, maxs.ctypes.data, n))
+        return mins, maxs
+
+    #: frames per call of ``transform_batch`` (one grid plane per frame)
+    TRANSFORM_MAX_FRAMES = 65535
+
+    def _warp_frames(self, images):
+        """(pointer table, residency flag, keep-alive) of the frames of ``transform_batch``: float32 H x W, or uint8 H x W x 3 for an
+        RGB plan; nothing is converted."""
+        fshape = tuple(self.shape) + ((3,) if self.RGB else ())
+        fdtype = numpy.dtype(numpy.uint8 if self.RGB else numpy.float32)
+        if hasattr(images, "shape") and hasattr(images, "dtype") and len(images.shape) == len(fshape) + 1:
+            images = [images[i] for i in range(int(images.shape[0]))]      # a stack: views of its frames
+        else:
+            images = list(images)
+        n = len(images)
+        if n > self.TRANSFORM_MAX_FRAMES:
+            raise ValueError("%d frames: more than %d" % (n, self.TRANSFORM_MAX_FRAMES))
+        ptrs = (C.c_void_p * max(n, 1))()
+        keep, dev_flags = [], set()
+        for i, image in enumerate(images):
+            if not (isinstance(image, numpy.ndarray) or hasattr(image, "data_ptr") or hasattr(image, "__cuda_array_interface__")):
+                raise RuntimeError("frame %d is neither a numpy array nor a tensor" % i)
+            ptr, is_dev, dtype, shape, k = _pointer_of(image)
+            if tuple(shape) != fshape:
+                raise RuntimeError("frame %d has shape %s, the plan warps %s" % (i, tuple(shape), fshape))
+            if numpy.dtype(dtype) != fdtype:
+                raise RuntimeError("frame %d is %s, the plan warps %s" % (i, dtype, fdtype))
+            dev_flags.add(int(bool(is_dev)))
+            ptrs[i] = ptr
+            keep.append(k)
+        if len(dev_flags) > 1:
+            raise RuntimeError("the frames of a batch must be all host arrays or all device tensors")
+        is_dev = dev_flags.pop() if dev_flags else 0
+        # (host frames are not stacked here: the library uploads every run of frames that lie back to back with one copy, so a
+        # stack is one copy and separate arrays are one each -- a host-side numpy.stack costs more than the copies it saves)
+        return ptrs, n, is_dev, keep
+
+    def transform_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, out="host"):
+        """Affine warp of S frames of the plan's shape in one launch (``siftmi_batch_transform``): frame s of the result is bit
+        for bit ``LinearAlign.transform(matrices[s], offsets[s], images[s], fills[s], mode)``.  One synchronisation, one upload of a
+        host stack (separate host arrays: one each) and one copy back of a host result.  A map with a non-finite entry gives ``fills[s]`` wherever it reaches
+        (all NaN: the whole plane).  Device memory: the result, plus the frames when they come from the host.
+
+        :param images: S frames, all numpy arrays or all device tensors, or one (S, H, W[, 3]) stack: float32 H x W, or uint8
+                       H x W x 3 for an RGB plan (nothing is converted)
+        :param matrices: (S, 2, 2) or (S, 4), acting on (y, x) as in ``LinearAlign.transform``
+        :param offsets: (S, 2)
+        :param fills: a scalar or (S,); for an RGB plan every value must lie in [0, 255]
+        :param out_shape: (OH, OW) of every output frame; None: the plan's shape
+        :param mode: 1 = bilinear, anything else = the nearest-lower tap
+        :param out: ``"host"``: a numpy array (in a pinned block of the library's pool when it fits, as ``LinearAlign.transform``
+                    returns it); ``"device"``: a torch tensor on the plan's device
+        :return: (S, OH, OW) float32, or (S, OH, OW, 3) uint8
+        """
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        ptrs, n, is_dev, keep = self._warp_frames(images)
+        maps = numpy.empty((n, 6), numpy.float32)
+        m = numpy.asarray(matrices, numpy.float32)
+        if m.shape not in ((n, 2, 2), (n, 4)) and not (n == 0 and m.size == 0):
+            raise ValueError("matrices must be (%d, 2, 2) or (%d, 4), not %s" % (n, n, m.shape))
+        o = numpy.asarray(offsets, numpy.float32)
+        if o.shape != (n, 2) and not (n == 0 and o.size == 0):
+            raise ValueError("offsets must be (%d, 2), not %s" % (n, o.shape))
+        maps[:, :4] = m.reshape(n, 4)
+        maps[:, 4:] = o.reshape(n, 2)
+        f = numpy.asarray(fills, numpy.float32)
+        if f.ndim == 0:
+            f = numpy.full(n, f, numpy.float32)
+        if f.shape != (n,):
+            raise ValueError("fills must be a scalar or (%d,), not %s" % (n, f.shape))
+        f = numpy.ascontiguousarray(f)
+        if self.RGB and n and not ((f >= 0) & (f <= 255)).all():
+            raise ValueError("an RGB fill must lie in [0, 255]: a value outside converts a float that uint8 cannot hold")
+        oh, ow = (int(v) for v in (self.shape if out_shape is None else out_shape))
+        if oh < 0 or ow < 0:
+            raise ValueError("negative output shape")
+        oshape, odtype = ((n, oh, ow, 3), numpy.uint8) if self.RGB else ((n, oh, ow), numpy.float32)
+        if out == "device":
+            import torch
+            result = torch.empty(oshape, dtype=torch.uint8 if self.RGB else torch.float32, device=torch.device("cuda", self.device))
+            optr = result.data_ptr()
+        else:
+            result = None
+            count = int(numpy.prod(oshape))
+            if self.pinned_results and count:
+                try:
+                    result = _lib.pinned_empty(count, odtype).reshape(oshape)
+                except MemoryError:                 # beyond the pool's limit (_lib.pinned_pool): an ordinary array
+                    result = None
+            if result is None:
+                result = numpy.empty(oshape, odtype)
+            optr = result.ctypes.data
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_batch_transform(self._handle, ptrs, n, is_dev, 3 if self.RGB else 1, optr, int(out == "device"),
+                                                         ow, oh, maps.ctypes.data, f.ctypes.data, int(mode), C.byref(ms)))
+        self.last_transform_ms = ms.value
+        del keep
+        return result
 
     def minmax(self):
         raise RuntimeError("BatchPlan keeps no per-frame min/max; use SiftPlan")

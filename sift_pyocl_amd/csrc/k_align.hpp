@@ -24,10 +24,10 @@ __device__ __forceinline__ float bilinear_mix(float tx, float ty, int tx_prev, i
     return ((float)(ty_prev + 1) - ty) * i1 + (ty - (float)ty_prev) * i2;
 }
 
-__global__ __launch_bounds__(256) void transform_kernel(const float *__restrict__ image, float *__restrict__ out, AffineArgs a,
-                                                        int W, int H, int OW, int OH) {
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= OW || y >= OH) return;
+// One output pixel of the float32 warp.  transform_kernel and transform_batch_kernel (k_align_batch.hpp) both call this, so the
+// single and the batched form cannot drift apart.  A non-finite tx or ty fails every comparison: `inside` is false, no index
+// is formed and the pixel is `fill`.
+__device__ __forceinline__ float transform_pixel(const float *__restrict__ image, const AffineArgs &a, int W, int H, int x, int y) {
     float tx = a.m2 * (float)y + a.m3 * (float)x;
     float ty = a.m0 * (float)y + a.m1 * (float)x;
     tx += a.off1; ty += a.off0;
@@ -46,7 +46,14 @@ __global__ __launch_bounds__(256) void transform_kernel(const float *__restrict_
     }
     if (tx >= (float)W + -0.5f) interp = a.fill;
     if (ty >= (float)H + -0.5f) interp = a.fill;
-    out[(size_t)y * OW + x] = interp;
+    return interp;
+}
+
+__global__ __launch_bounds__(256) void transform_kernel(const float *__restrict__ image, float *__restrict__ out, AffineArgs a,
+                                                        int W, int H, int OW, int OH) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= OW || y >= OH) return;
+    out[(size_t)y * OW + x] = transform_pixel(image, a, W, H, x, y);
 }
 
 // RGB8: one thread produces 4 consecutive output pixels = 12 bytes, stored as three dwords when the row segment is
@@ -89,11 +96,12 @@ __device__ __forceinline__ void transform_rgb_pixel(const uint8_t *__restrict__ 
     }
 }
 
-__global__ __launch_bounds__(256) void transform_rgb_kernel(const uint8_t *__restrict__ image, uint8_t *__restrict__ out, AffineArgs a,
-                                                            int W, int H, int OW, int OH) {
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= OW || y >= OH) return;
-    uint8_t *o = out + 3 * ((size_t)y * OW + x0);
+// The 4 pixels from column x0 of row y, written to `o` (the address of pixel (y, x0) in the output).  Three dword stores when
+// all four pixels exist and `o` ITSELF is 4-byte aligned -- the address is tested, not the column: an output row starts at any
+// alignment mod 4 (3 * OW bytes per row, and in a stack of frames 3 * OH * OW bytes per frame).  Shared by
+// transform_rgb_kernel and transform_rgb_batch_kernel (k_align_batch.hpp).
+__device__ __forceinline__ void transform_rgb_quad(const uint8_t *__restrict__ image, const AffineArgs &a, int W, int H, int OW,
+                                                   int x0, int y, uint8_t *__restrict__ o) {
     if (x0 + 4 <= OW && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
         uint8_t b[12];
 #pragma unroll
@@ -111,6 +119,13 @@ __global__ __launch_bounds__(256) void transform_rgb_kernel(const uint8_t *__res
             o[3 * k] = b[0]; o[3 * k + 1] = b[1]; o[3 * k + 2] = b[2];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void transform_rgb_kernel(const uint8_t *__restrict__ image, uint8_t *__restrict__ out, AffineArgs a,
+                                                            int W, int H, int OW, int OH) {
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= OW || y >= OH) return;
+    transform_rgb_quad(image, a, W, H, OW, x0, y, out + 3 * ((size_t)y * OW + x0));
 }
 
 }  // namespace siftk

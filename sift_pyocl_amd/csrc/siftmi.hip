@@ -22,6 +22,7 @@
 #include "k_keypoint.hpp"
 #include "k_descriptor.hpp"
 #include "k_align.hpp"
+#include "k_align_batch.hpp"
 #include "k_pyramid.hpp"
 #include "k_tail.hpp"
 #include "siftmath.hpp"
@@ -1675,6 +1676,15 @@ struct siftmi_batch {
     const void *const *cur_images = nullptr;       // the frames of the call in progress (a lane re-runs its frame after a tail time-out)
     int32_t cur_dtype = 0, cur_is_device = 0;
     int64_t tail_retries = 0;                      // frames re-run since the batch was created
+    // min / max of every frame of the batch, recorded under the frame's index as its lane retires (siftmi_batch_minmax);
+    // mm_frames: frames of the last FINISHED batch, -1 while none has finished (none yet, one in progress, the last one failed)
+    std::vector<float> mins, maxs;
+    int64_t mm_frames = -1;
+    // siftmi_batch_transform: staging of host frames and of a host output, the table of frames (pinned block and its device
+    // copy), all grown on demand and counted by siftmi_batch_info
+    void *warp_in = nullptr, *warp_out = nullptr, *warp_tab = nullptr, *warp_tab_host = nullptr;
+    size_t warp_in_bytes = 0, warp_out_bytes = 0, warp_tab_bytes = 0, warp_tab_host_bytes = 0;
+    hipEvent_t ev_wa = nullptr, ev_wb = nullptr;
 };
 extern "C" {
 
@@ -1686,6 +1696,10 @@ int siftmi_batch_destroy(siftmi_batch *b) {
     for (void *q : b->ring) hipFree(q);
     for (hipEvent_t e : b->ring_ev) hipEventDestroy(e);
     if (b->copy_stream) hipStreamDestroy(b->copy_stream);
+    for (void *q : {b->warp_in, b->warp_out, b->warp_tab}) if (q) hipFree(q);
+    if (b->warp_tab_host) hipHostFree(b->warp_tab_host);
+    if (b->ev_wa) hipEventDestroy(b->ev_wa);
+    if (b->ev_wb) hipEventDestroy(b->ev_wb);
     delete b;
     return SIFTMI_OK;
 }
@@ -1748,7 +1762,8 @@ int siftmi_batch_info(const siftmi_batch *b, int32_t *lanes, int64_t *bytes_allo
     if (!b) return fail(SIFTMI_EINVAL, "null batch");
     if (lanes) *lanes = (int32_t)b->lanes.size();
     if (bytes_allocated) {
-        int64_t t = (int64_t)b->arena_cap + (int64_t)(b->ring.size() * b->ring_bytes);
+        int64_t t = (int64_t)b->arena_cap + (int64_t)(b->ring.size() * b->ring_bytes) +
+                    (int64_t)(b->warp_in_bytes + b->warp_out_bytes + b->warp_tab_bytes);
         for (const siftmi_plan *p : b->lanes) t += p->bytes;
         *bytes_allocated = t;
     }
@@ -1800,6 +1815,7 @@ int batch_retire(siftmi_batch *b, size_t l, int32_t *overflow) {
             HIPCHK(hipStreamSynchronize(p->fin));
         }
         b->counts[(size_t)img] = n;
+        b->mins[(size_t)img] = p->last_min; b->maxs[(size_t)img] = p->last_max;
         b->offsets[(size_t)img] = -1;                 // delivered
         b->retired++;
         b->lane_image[l] = -1;
@@ -1825,6 +1841,7 @@ int batch_retire(siftmi_batch *b, size_t l, int32_t *overflow) {
     if (n > 0)
         HIPCHK(hipMemcpyAsync(b->arena + b->arena_used, p->records, bytes, hipMemcpyDeviceToDevice, p->fin));
     b->counts[(size_t)img] = n;
+    b->mins[(size_t)img] = p->last_min; b->maxs[(size_t)img] = p->last_max;
     b->offsets[(size_t)img] = (int64_t)(b->arena_used / sizeof(KpRecord));
     b->arena_used = need;
     b->retired++;
@@ -1868,6 +1885,9 @@ int siftmi_batch_keypoints_into(siftmi_batch *b, const void *const *images, int3
     b->cur_images = images; b->cur_dtype = image_dtype; b->cur_is_device = images_are_device;
     b->counts.assign((size_t)n_images, 0);
     b->offsets.assign((size_t)n_images, 0);
+    b->mm_frames = -1;
+    b->mins.assign((size_t)n_images, 0.0f);
+    b->maxs.assign((size_t)n_images, 0.0f);
     const size_t L = b->lanes.size();
     int rc = SIFTMI_OK;
     // (from here on an error must not return at once: the lanes and the copy stream may be reading the caller's frames or
@@ -1938,6 +1958,7 @@ int siftmi_batch_keypoints_into(siftmi_batch *b, const void *const *images, int3
     HIPCHK(hipDeviceSynchronize());                            // the parking copies
     for (int i = 0; i < n_images; i++) { counts[i] = b->counts[(size_t)i]; offsets[i] = b->offsets[(size_t)i]; }
     *total_parked = (int64_t)(b->arena_used / sizeof(KpRecord));
+    b->mm_frames = n_images;
     return SIFTMI_OK;
 }
 
@@ -1954,6 +1975,109 @@ int siftmi_batch_fetch(siftmi_batch *b, siftmi_keypoint *out, int32_t out_is_dev
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipMemcpy(out, b->arena + (size_t)first * sizeof(KpRecord), (size_t)count * sizeof(KpRecord),
                      out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return SIFTMI_OK;
+}
+
+int siftmi_batch_minmax(const siftmi_batch *b, float *mins, float *maxs, int32_t n_images) {
+    if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (b->mm_frames < 0) return fail(SIFTMI_EINVAL, "no batch has finished on this handle");
+    if ((int64_t)n_images != b->mm_frames) return fail(SIFTMI_EINVAL, "the last batch had %lld frames, not %d", (long long)b->mm_frames, n_images);
+    for (int32_t i = 0; i < n_images; i++) {
+        if (mins) mins[i] = b->mins[(size_t)i];
+        if (maxs) maxs[i] = b->maxs[(size_t)i];
+    }
+    return SIFTMI_OK;
+}
+
+namespace {
+// a device buffer of the batch handle, replaced by a larger one when `need` outgrows it (nothing of its contents is kept)
+int grow_device(void **ptr, size_t *cap, size_t need) {
+    if (*ptr && need <= *cap) return SIFTMI_OK;
+    if (*ptr) { HIPCHK(hipDeviceSynchronize()); hipFree(*ptr); }
+    *ptr = nullptr; *cap = 0;
+    hipError_t e = hipMalloc(ptr, need ? need : 16);
+    if (e != hipSuccess) { *ptr = nullptr; return fail(SIFTMI_ENOMEM, "hipMalloc(%zu): %s", need, hipGetErrorString(e)); }
+    *cap = need ? need : 16;
+    return SIFTMI_OK;
+}
+}  // namespace
+
+// The warp of siftmi_plan_transform for n frames in one launch (k_align_batch.hpp).
+int siftmi_batch_transform(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device,
+                           int32_t channels, void *out, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps,
+                           const float *fills, int32_t mode, double *kernel_ms) {
+    if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (n_images < 0) return fail(SIFTMI_EINVAL, "negative image count");
+    if (n_images > 65535) return fail(SIFTMI_EINVAL, "%d frames: more than 65535 (one grid plane per frame)", n_images);
+    if (channels != 1 && channels != 3) return fail(SIFTMI_EINVAL, "channels must be 1 (float32) or 3 (RGB8), got %d", channels);
+    if (OW < 0 || OH < 0) return fail(SIFTMI_EINVAL, "negative output shape");
+    if (OH > 4 * 65535) return fail(SIFTMI_EINVAL, "output height %d: more than %d rows (4 per grid row)", OH, 4 * 65535);
+    const bool empty = n_images == 0 || OW == 0 || OH == 0;
+    if (n_images > 0 && (!images || !maps || !fills)) return fail(SIFTMI_EINVAL, "null argument");
+    if (!empty && !out) return fail(SIFTMI_EINVAL, "null output");
+    for (int32_t i = 0; i < n_images; i++) if (!images[i]) return fail(SIFTMI_EINVAL, "null image %d", i);
+    if (kernel_ms) *kernel_ms = 0;
+    if (empty || b->lanes.empty()) return SIFTMI_OK;
+    HIPCHK(hipSetDevice(b->device));
+    siftmi_plan *p0 = b->lanes[0];
+    hipStream_t stream = p0->stream;               // every lane is idle between two calls on the handle
+    const int W = p0->W, H = p0->H;
+    const size_t px = channels == 1 ? 4 : 3;
+    const size_t in_bytes = (size_t)W * H * px, frame_out = (size_t)OW * OH * px, out_bytes = frame_out * (size_t)n_images;
+    // a device pointer on either side: ordered after what the NULL stream was given for it (siftmi.h, conventions)
+    if (images_are_device || out_is_device) HIPCHK(hipDeviceSynchronize());
+    int rc;
+    if (!images_are_device && (rc = grow_device(&b->warp_in, &b->warp_in_bytes, in_bytes * (size_t)n_images))) return rc;
+    if (!out_is_device && (rc = grow_device(&b->warp_out, &b->warp_out_bytes, out_bytes))) return rc;
+    const size_t tab_bytes = sizeof(WarpFrame) * (size_t)n_images;
+    if ((rc = grow_device(&b->warp_tab, &b->warp_tab_bytes, tab_bytes))) return rc;
+    if (b->warp_tab_host_bytes < tab_bytes) {
+        if (b->warp_tab_host) hipHostFree(b->warp_tab_host);
+        b->warp_tab_host = nullptr; b->warp_tab_host_bytes = 0;
+        size_t cap = 4096;
+        while (cap < tab_bytes) cap *= 2;
+        hipError_t e = hipHostMalloc(&b->warp_tab_host, cap, hipHostMallocDefault);
+        if (e != hipSuccess) { b->warp_tab_host = nullptr; return fail(SIFTMI_ENOMEM, "hipHostMalloc(%zu): %s", cap, hipGetErrorString(e)); }
+        b->warp_tab_host_bytes = cap;
+    }
+    if (!b->ev_wa) { HIPCHK(hipEventCreate(&b->ev_wa)); HIPCHK(hipEventCreate(&b->ev_wb)); }
+    // host frames: one copy per run of frames that lie back to back in host memory (a stack is ONE copy)
+    if (!images_are_device) {
+        for (int32_t i = 0; i < n_images;) {
+            int32_t j = i + 1;
+            while (j < n_images && (const uint8_t *)images[j] == (const uint8_t *)images[j - 1] + in_bytes) j++;
+            hipError_t e = hipMemcpyAsync((uint8_t *)b->warp_in + (size_t)i * in_bytes, images[i], in_bytes * (size_t)(j - i), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(SIFTMI_EDEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e)); }
+            i = j;
+        }
+    }
+    WarpFrame *tab = static_cast<WarpFrame *>(b->warp_tab_host);
+    for (int32_t i = 0; i < n_images; i++) {
+        const float *m = maps + 6 * (size_t)i;
+        tab[i].image = images_are_device ? images[i] : (const void *)((const uint8_t *)b->warp_in + (size_t)i * in_bytes);
+        tab[i].a = AffineArgs{m[0], m[1], m[2], m[3], m[4], m[5], fills[i], mode};
+    }
+    HIPCHK(hipMemcpyAsync(b->warp_tab, tab, tab_bytes, hipMemcpyHostToDevice, stream));
+    void *dst = out_is_device ? out : b->warp_out;
+    const int xcols = channels == 1 ? 64 : 256;   // RGB: 4 pixels per thread
+    const dim3 grid((unsigned)((OW + xcols - 1) / xcols), (unsigned)((OH + 3) / 4), (unsigned)n_images), block(64, 4);
+    hipEventRecord(b->ev_wa, stream);
+    if (channels == 1)
+        hipLaunchKernelGGL(transform_batch_kernel, grid, block, 0, stream, (const WarpFrame *)b->warp_tab, (float *)dst, W, H, OW, OH);
+    else
+        hipLaunchKernelGGL(transform_rgb_batch_kernel, grid, block, 0, stream, (const WarpFrame *)b->warp_tab, (uint8_t *)dst, W, H, OW, OH);
+    hipEventRecord(b->ev_wb, stream);
+    if (!out_is_device) {
+        hipError_t e = hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(SIFTMI_EDEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e)); }
+    }
+    HIPCHK(hipStreamSynchronize(stream));          // (the pinned table and the caller's frames are free again from here on)
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, b->ev_wa, b->ev_wb);
+        *kernel_ms = ms;
+    }
     return SIFTMI_OK;
 }
 
