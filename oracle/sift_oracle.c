@@ -356,7 +356,10 @@ static void so_orientation_one(const so_kp4 k, const float *grad, const float *o
             distsq += dif * dif;
             if (gval > 0.0f && distsq < lim) {
                 const float a = ori[(size_t)r * W + c];
-                int bin = (int)(36.0f * (a + SO_PI_F + 0.001f) / (2.0f * SO_PI_F));
+                /* (int)NaN (the orientation next to an inf / NaN pixel; its magnitude can be +inf) is undefined in C;
+                 * x86 cvttss2si yields INT_MIN, which fails `bin >= 0`: no vote.  Made explicit here. */
+                const float fbin = 36.0f * (a + SO_PI_F + 0.001f) / (2.0f * SO_PI_F);
+                int bin = (fbin == fbin) ? (int)fbin : -1;
                 if (bin >= 0 && bin <= 36) {
                     if (bin > 35) bin = 35;
                     hist[bin] += om_expf(-distsq / two_s2) * gval;
@@ -453,7 +456,8 @@ void so_descriptor(const so_kp4 *kps, uint8_t *desc, const float *grad, const fl
                 const float oval = 4.0f * o * SO_1_PI_F;
                 const int ri = (int)((rx >= 0.0f) ? rx : rx - 1.0f);
                 const int ci = (int)((cx >= 0.0f) ? cx : cx - 1.0f);
-                const int oi = (int)((oval >= 0.0f) ? oval : oval - 1.0f);
+                /* a NaN orientation: (int)NaN is INT_MIN on x86 and fails `oi >= 0`, the sample is skipped (made explicit) */
+                const int oi = (oval == oval) ? (int)((oval >= 0.0f) ? oval : oval - 1.0f) : -1;
                 const float rf = rx - (float)ri, cf = cx - (float)ci, of = oval - (float)oi;
                 if (!(ri >= -1 && ri < 4 && oi >= 0 && oi <= 8 && rf >= 0.0f && rf <= 1.0f)) continue;
                 for (int a = 0; a < 2; a++) {

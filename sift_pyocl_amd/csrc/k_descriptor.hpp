@@ -333,7 +333,10 @@ __device__ __forceinline__ void desc_eval4(const DescWindow &w, const DescEvalSt
     const desc_f2 F = RC - (desc_f2){(float)ri, (float)ci};
     const float rf = F.x, cf = F.y, of = oval - (float)oi;
     const desc_f2 G = (desc_f2){1.0f, 1.0f} - F;
-    const bool contributes = live && ri >= -1 && ri < 4 && oi >= 0 && oi <= 8 && rf >= 0.0f && rf <= 1.0f;
+    // `oi >= 0` (keypoints_cpu.cl:89) as a test on the float: after the loops o >= 0, so it holds for every number.  A NaN
+    // orientation (the gradient of a sample next to an inf or NaN pixel) gives (int)NaN == INT_MIN in the reference, which
+    // skips the sample; the conversion here gives 0 and would add its NaN values to the cell.
+    const bool contributes = live && ri >= -1 && ri < 4 && oval >= 0.0f && oi <= 8 && rf >= 0.0f && rf <= 1.0f;
     // the eight values, products in the reference's order: ((mag * row weight) * column weight) * orientation weight
     const desc_f2 RW = (desc_f2){mag, mag} * (desc_f2){G.x, rf};                 // a = 0, 1
     const desc_f2 CWa = (desc_f2){RW.x, RW.x} * (desc_f2){G.y, cf};              // a = 0: bb = 0, 1
@@ -342,8 +345,12 @@ __device__ __forceinline__ void desc_eval4(const DescWindow &w, const DescEvalSt
     const desc_f2 v00 = (desc_f2){CWa.x, CWa.x} * OW, v01 = (desc_f2){CWa.y, CWa.y} * OW;
     const desc_f2 v10 = (desc_f2){CWb.x, CWb.x} * OW, v11 = (desc_f2){CWb.y, CWb.y} * OW;
     // the eight bins (rb * 4 + cb) * 8 + ob.  Orientation bin oi + 1 wraps to 0; oi == 8 happens only for oval == 8.0f
-    // exactly (o == 2*pi_f), where of == 0: e = 0 adds cw*1 to bin 0, e = 1 would add cw*0 == +0 to bin 0 again (no
-    // effect on a non-negative sum); here such a sample counts as one of orientation bin 0 whose upper value is +0.
+    // exactly (o == 2*pi_f -- the loops leave o <= 2*pi_f -- or the few floats below it whose product rounds to 8),
+    // where of == 0: e = 0 adds cw*1 to bin 0, e = 1 would add cw*0 == +0 to bin 0 again (no effect on a non-negative
+    // sum); here such a sample counts as one of orientation bin 0 whose upper value is +0.  For an infinite cw the
+    // reference's second addition is inf * 0 = NaN where this one adds +0: the bin ends as NaN there and as inf here,
+    // and either way every byte of the descriptor is 0 (a non-finite sum makes the first norm inf or NaN, the products
+    // 0 or NaN).  tests/test_gpu_keypoint_cases.py runs hundreds of such samples per keypoint (`ramps`, `small`, `huge`).
     const bool nd = oi != 8;
     cval[0] = v00.x; cval[1] = nd ? v00.y : 0.0f; cval[2] = v01.x; cval[3] = nd ? v01.y : 0.0f;
     cval[4] = v10.x; cval[5] = nd ? v10.y : 0.0f; cval[6] = v11.x; cval[7] = nd ? v11.y : 0.0f;

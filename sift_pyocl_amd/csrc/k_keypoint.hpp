@@ -380,8 +380,12 @@ __global__ __launch_bounds__(256) void orientation_kernel(OctaveTable tab, float
                         if (!MAPS && !ok_a) a = siftmath::atan2f_(-gy, gx);
                         if (!ok_e) ew = siftmath::expf_(earg);
                     }
-                    bin = (int)siftmath::div_by_reciprocal(36.0f * (a + SM_PI_F + 0.001f), 2.0f * SM_PI_F, 1.0f / (2.0f * SM_PI_F));
-                    valid = (bin >= 0) && (bin <= 36);
+                    // A NaN orientation (a gradient of inf or NaN; its magnitude can be +inf and pass `gval > 0`) does not vote:
+                    // the reference's (int)NaN is INT_MIN and fails `bin >= 0`; here the conversion gives 0, so the test is
+                    // made on the float: fbin > -1 <=> (int)fbin >= 0 for every number, false for NaN.
+                    const float fbin = siftmath::div_by_reciprocal(36.0f * (a + SM_PI_F + 0.001f), 2.0f * SM_PI_F, 1.0f / (2.0f * SM_PI_F));
+                    bin = (int)fbin;
+                    valid = (fbin > -1.0f) && (bin <= 36);
                     bin = min(max(bin, 0), 35);
                     val = ew * gval;
                 }
@@ -634,7 +638,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                 const int ci = (int)((cx >= 0.0f) ? cx : cx - 1.0f);
                 const int oi = (int)((oval >= 0.0f) ? oval : oval - 1.0f);
                 const float rf = rx - (float)ri, cf = cx - (float)ci, of = oval - (float)oi;
-                const bool contributes = ri >= -1 && ri < 4 && oi >= 0 && oi <= 8 && rf >= 0.0f && rf <= 1.0f;
+                // `oi >= 0` as a test on the float: after the loops o >= 0, so it holds for every number; for a NaN orientation
+                // the reference's (int)NaN is INT_MIN and the sample is skipped, where the conversion here gives 0
+                const bool contributes = ri >= -1 && ri < 4 && oval >= 0.0f && oi <= 8 && rf >= 0.0f && rf <= 1.0f;
                 if (contributes) {
                     const unsigned int bit = 1u << (lane & 31);
                     const int word = lane >> 5;

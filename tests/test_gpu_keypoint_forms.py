@@ -29,10 +29,10 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _params():
+def _params(ori_sigma=1.5):
     from sift_pyocl_amd import _lib
     return _lib.Params(init_sigma=1.6, peak_thresh=F(255.0 * 0.04 / 3.0), edge_thresh0=F(0.08), edge_thresh=F(0.06),
-                       ori_sigma=F(1.5), border_dist=5, octave_max=0, pix_per_kp=10, double_im_size=0)
+                       ori_sigma=F(ori_sigma), border_dist=5, octave_max=0, pix_per_kp=10, double_im_size=0)
 
 
 def desc_radius(sigma, octsize):
@@ -76,15 +76,19 @@ def _oracle_descriptors(oracle, blurs, octsize, kk, ss):
     return want
 
 
-def _oracle_orientation(oracle, blurs, kps, ss):
+def _oracle_orientation(oracle, blurs, kps, ss, octsize=1, ori_sigma=1.5):
     """the oracle's oriented keypoints of a refined list, NaN rows dropped, as sorted rows (x, y, sigma, angle, scale)"""
     out = []
+    par = oracle.default_params()
+    par.ori_sigma = F(ori_sigma)
     for s in np.unique(ss):
         sel = kps[ss == s]
         eg, eo = oracle.gradient(blurs[s])
         buf = np.full((len(sel) * 8 + 8, 4), -1, np.float32); buf[:len(sel)] = sel
-        okp, cnt = oracle.orientation(buf, eg, eo, 1, 0, len(sel), capacity=len(buf), par=oracle.default_params())
-        okp = okp[:cnt][~np.isnan(okp[:cnt].sum(axis=1))]
+        okp, cnt = oracle.orientation(buf, eg, eo, octsize, 0, len(sel), capacity=len(buf), par=par)
+        assert cnt <= len(buf)
+        okp = okp[:cnt][okp[:cnt, 1] >= 0]                          # (holes of the list stay where they were: row -1)
+        okp = okp[~np.isnan(okp.sum(axis=1))]
         out.append(np.concatenate([okp, np.full((len(okp), 1), s, np.float32)], axis=1))
     return sort_rows(np.concatenate(out))
 
@@ -108,16 +112,16 @@ def _check_descriptor_forms(siftlib, blurs, octsize, kk, ss, want, what, forms=D
                 what, form, blocks, len(bad), kk[bad[:4]])
 
 
-def _check_orientation_forms(siftlib, blurs, kps, ss, want, what, forms=ORI_FORMS, blocks_list=BLOCKS):
+def _check_orientation_forms(siftlib, blurs, kps, ss, want, what, forms=ORI_FORMS, blocks_list=BLOCKS, octsize=1, ori_sigma=1.5):
     H, W = blurs.shape[1:]
     kps = np.ascontiguousarray(kps, np.float32); ss = np.ascontiguousarray(ss, np.int32)
-    par = _params()
+    par = _params(ori_sigma)
     cap = len(kps) * 8 + 8
     for form in forms:
         for blocks in blocks_list:
             out = np.zeros((cap, 4), np.float32); osc = np.zeros(cap, np.int32)
             no, used = C.c_int64(-1), C.c_int32(-1)
-            rc = siftlib.siftmi_stage_orientation_ex(0, _p(blurs), W, H, 1, _p(kps), _p(ss), len(kps), C.byref(par), _p(out), _p(osc),
+            rc = siftlib.siftmi_stage_orientation_ex(0, _p(blurs), W, H, octsize, _p(kps), _p(ss), len(kps), C.byref(par), _p(out), _p(osc),
                                                      cap, C.byref(no), form, blocks, C.byref(used))
             assert rc == 0 and used.value == form, (what, form, blocks, rc, used.value)
             assert no.value == len(want), "%s, form %d, %d workgroups: %d oriented keypoints, oracle %d" % (what, form, blocks, no.value, len(want))
