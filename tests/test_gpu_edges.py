@@ -354,6 +354,11 @@ def _nan_frames(shape):
         f = base.copy()
         f.flat[where] = np.nan
         out[name] = f
+    # the complement of "tail": NaN everywhere but the float4 tail, where the extremes then are -- a kernel that never reads
+    # the tail passes "tail" and fails this one
+    f = np.full(shape, np.nan, np.float32)
+    f.flat[n - (n % 4 or 1):] = base.flat[n - (n % 4 or 1):]
+    out["only_tail"] = f
     out["all"] = np.full(shape, np.nan, np.float32)
     return out
 
@@ -376,14 +381,16 @@ def test_stage_minmax_ignores_nan(siftlib, oracle, shape):
             continue
         assert (np.float32(mn.value), np.float32(mx.value)) == (emn, emx) == oracle.minmax(f), (shape, name)
         exp = oracle.normalize(f, emn, emx)
-        assert np.array_equal(np.isnan(out), np.isnan(f)) and np.array_equal(out, exp, equal_nan=True), (shape, name)
+        nan = np.isnan(f) | (emn == emx)                              # a single finite pixel: min == max, 0 / 0 there as well
+        assert np.array_equal(np.isnan(out), nan) and np.array_equal(out, exp, equal_nan=True), (shape, name)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [TILED, (131, 97)])
 def test_plan_minmax_ignores_nan(siftlib, shape):
     """SiftPlan.minmax() of frames with NaN pixels: every fourth row NaN (pixel 0 included, so every plane is NaN after the
-    initial blur and no keypoint is formed), and a constant frame with NaN at pixel 0 and in the float4 tail."""
+    initial blur and no keypoint is formed), a constant frame with NaN at pixel 0 and in the float4 tail, and a frame that is
+    finite in the float4 tail alone."""
     import sift_pyocl_amd as sp
     rng = np.random.default_rng(9)
     rows = (rng.random(shape, dtype=np.float32) - 0.5) * 300
@@ -391,6 +398,6 @@ def test_plan_minmax_ignores_nan(siftlib, shape):
     flat = np.full(shape, 2.5, np.float32)
     flat.flat[0] = flat.flat[-1] = np.nan
     plan = sp.SiftPlan(template=rows)
-    for f in (rows, flat):
+    for f in (rows, flat, _nan_frames(shape)["only_tail"]):
         plan.keypoints(f)
         assert plan.minmax() == (np.nanmin(f), np.nanmax(f))

@@ -29,7 +29,10 @@ def as_f32(img):
     return img.astype(np.float32)          # numpy int -> float32 rounds to nearest even, as the OpenCL cast
 
 
-@pytest.mark.parametrize("shape", [(200, 300), (600, 1100)])          # tile kernel / marching kernel for the initial blur
+# Both even shapes are below the marching blur's planes (the tile kernel takes their initial blur) and their pixel counts are
+# multiples of 16: only (201, 301) leaves the typed min/max a scalar tail (60 501 pixels: 1 behind the last chunk of 4, 5
+# behind the last chunk of 8 or 16).
+@pytest.mark.parametrize("shape", [(200, 300), (600, 1100), (201, 301)])
 @pytest.mark.parametrize("name", ["uint8", "uint16", "uint32", "uint64", "int32", "int64"])
 def test_integer_frames(siftlib, oracle, name, shape):
     import sift_pyocl_amd as sp
@@ -48,7 +51,7 @@ def test_integer_frames(siftlib, oracle, name, shape):
     assert_same_keypoints(plain.keypoints(img), want, "%s frame, convert pass" % name)
 
 
-@pytest.mark.parametrize("shape", [(180, 260), (520, 1030)])
+@pytest.mark.parametrize("shape", [(180, 260), (520, 1030), (201, 301)])     # (201, 301): 5 pixels behind the last chunk of 16
 def test_rgb_frames(siftlib, oracle, shape):
     import sift_pyocl_amd as sp
     rng = np.random.default_rng(shape[1])
