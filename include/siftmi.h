@@ -436,6 +436,29 @@ int siftmi_match_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1
                        const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
                        const int64_t *counts1, const int64_t *counts2, float ratio_th, int32_t mutual, int32_t part_len,
                        int32_t *pairs, int32_t pairs_is_device, int64_t *pair_counts);
+/* siftmi_match_window for S segment pairs in one set of launches and one stream synchronisation (extension; DESIGN.md section 7
+ * row 16, restated in numpy by tests/match_window_batch_ref.py).  The lists, n_segments, counts1 (NULL: one shared first list),
+ * counts2, pairs, pairs_is_device and pair_counts are siftmi_match_batch's, and so is the result's layout: the pairs of segment s
+ * are the rows [sum(pair_counts[0..s)), + pair_counts[s]) of `pairs`, indices local to the segment, in ascending i.  Segment s gets
+ * siftmi_match_window's rule on its own two lists with its own shift: exactly the set of pairs of that call on the segment's
+ * slices.  The result does not depend on grid_max, on scheduling or on the records of other segments.  A segment with an empty
+ * list on either side gives no pair; a query with exactly one candidate always pairs with it.
+ *   wx, wy       half widths of the window, >= 0; +inf is allowed
+ *   shifts       host, 2 * n_segments floats: (sx, sy) of every segment, finite
+ *   mutual       keep (i, j) only if i is also the nearest candidate of j inside segment s (the same predicate, same operand
+ *                order), ties to the smallest i
+ *   grid_max     0 (the library chooses: 256) or 1 .. 256, the most cells per axis of any segment's grid (test hook)
+ * Both lists are used where they lie (host lists are staged).  The region of interest plays no part and the matcher's pair
+ * capacity (`size`) is left alone.  When no segment has an element on both sides nothing is launched.
+ * siftmi_match_last_kernel_ms reports all kernels of the call, siftmi_match_last_stage_ms its stages as for siftmi_match_batch.
+ * SIFTMI_EINVAL, nothing launched, nothing written: a null matcher, n_segments outside 0 .. 65 535, a negative count, counts that do
+ * not add up to n1 / n2, a ratio_th that is not <= 1, a negative or NaN window, a shift that is not finite, grid_max outside
+ * 0 .. 256, a null list, counts2, shifts, pair_counts or pairs where it is needed, more than 2^28 - 1 records on a side or
+ * queries in all, or more work than the tables hold (2^30 work items a direction). */
+int siftmi_match_window_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                              const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                              const int64_t *counts1, const int64_t *counts2, float ratio_th, float wx, float wy, const float *shifts,
+                              int32_t mutual, int32_t grid_max, int32_t *pairs, int32_t pairs_is_device, int64_t *pair_counts);
 /* siftmi_match_fit for every segment of a batch in one set of launches and one stream synchronisation (extension; DESIGN.md
  * section 7 row 13, restated by tests/estimate_batch_ref.py).  The lists, n_segments, counts1 (NULL: one shared first list) and
  * counts2 are siftmi_match_batch's arguments and `pairs` / `pair_counts` its results, unchanged: the pairs of segment s are the rows

@@ -486,6 +486,41 @@ class LinearAlign(object):
         :param lanes: lanes of the ``BatchPlan`` (created on first use); None: its default for the frame size
         :return: the aligned stack (S, OH, OW[, 3]), or the dict
         """
+        return self._align_batch(images, lambda ref, records, counts: self.match.match_batch(ref, None, records, counts, ratio=match_ratio, out="device"),
+                                 shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes)
+
+    def align_batch_window(self, images, max_shift, expected_shift=None, shift_only=False, robust=False, robust_tol=3.0, robust_hyp=2048,
+                           match_ratio=None, return_all=False, out="host", lanes=None):
+        """``align_batch`` with the windowed matcher (extension): the match stage is
+        ``MatchPlan.match_window_batch(ref, None, records, counts, window=max_shift, window_shift=expected_shift or (0, 0),
+        ratio=match_ratio, out="device")``, which compares each reference keypoint only with the keypoints of a frame within
+        ``max_shift`` pixels of its position moved by that frame's ``expected_shift`` -- many times fewer descriptor pairs on
+        dense frames.  Every other stage, the decision rule and the result are ``align_batch``'s; ``max_shift=inf`` without an
+        expected shift gives ``align_batch``'s results.  (The keywords live in a method of their own because ``align_batch``'s
+        parameter list is pinned by the tests of row 15.)
+
+        The warnings of ``align(max_shift=)`` hold per frame.  When the true displacement of a frame lies outside the window, the
+        true partners are not candidates: expect few or wrong matches, not an error.  On sparse frames a keypoint with a single
+        candidate always pairs with it; ``robust=True`` is recommended there.
+
+        :param images: as for ``align_batch``
+        :param max_shift: bound in pixels on how far a keypoint of a frame lies from its partner in the reference frame (after
+                       the expected shift), a scalar or an (x, y) pair; ``inf`` is allowed.  Required
+        :param expected_shift: None (no displacement expected), one ``(sx, sy)`` for all frames or an (S, 2) array with one per
+                       frame, in (x, y) order: where a frame's keypoints are expected relative to their partners in the reference
+        :param shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes: as for ``align_batch``
+        :return: the aligned stack (S, OH, OW[, 3]), or ``align_batch``'s dict
+        """
+        if max_shift is None:
+            raise ValueError("align_batch_window needs max_shift; without a window the call is align_batch")
+        shift = (0.0, 0.0) if expected_shift is None else expected_shift
+        return self._align_batch(images, lambda ref, records, counts: self.match.match_window_batch(
+            ref, None, records, counts, window=max_shift, window_shift=shift, ratio=match_ratio, out="device"),
+            shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes)
+
+    def _align_batch(self, images, matcher, shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes):
+        """the body of ``align_batch``; ``matcher(ref_list, records, counts)`` returns ``(pairs, pair_counts)`` with the pairs on
+        the device"""
         import torch
         if out not in ("host", "device"):
             raise ValueError("out must be 'host' or 'device', not %r" % (out,))
@@ -499,7 +534,7 @@ class LinearAlign(object):
             counts = numpy.asarray(counts, numpy.int64).reshape(S)
             dev = torch.device("cuda", self.device)
             if self.ref_kp.size and int(counts.sum()):
-                pairs, pc = self.match.match_batch(ref_list, None, records, counts, ratio=match_ratio, out="device")
+                pairs, pc = matcher(ref_list, records, counts)
             else:
                 pairs, pc = torch.empty((0, 2), dtype=torch.int32, device=dev), numpy.zeros(S, numpy.int64)
             starts = numpy.concatenate([[0], numpy.cumsum(pc)]).astype(numpy.int64)

@@ -1,5 +1,6 @@
 // match.hip -- MatchPlan's side of libsiftmi.so: the brute-force matcher (k_match.hpp), its windowed form
-// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp), their exact median displacement (k_shift.hpp), the matcher over a batch of segment pairs (k_match_batch.hpp) the fit and the median of every segment of such a batch at once (k_estimate_batch.hpp) and the consensus filter over every segment at once (k_consensus_batch.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+// (k_match_window.hpp), the k-nearest-neighbour scans that return distances (k_knn.hpp: L1, k_knn_l2.hpp: squared Euclidean, k_knn_window.hpp: either one inside a search window), the consensus filter over the pairs (k_consensus.hpp) the least-squares affine map of the pairs (k_fit.hpp), their exact median displacement (k_shift.hpp), the matcher over a batch of segment pairs (k_match_batch.hpp) the fit and the median of every segment of such a batch at once (k_estimate_batch.hpp) and the consensus filter over every segment at once (k_consensus_batch.hpp) and the windowed matcher over a batch of segment pairs (k_match_window_batch.hpp).  Shares nothing with the SIFT pipeline of siftmi.hip but the error path (host_common.hpp).
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -17,6 +18,7 @@
 #include "k_match_batch.hpp"
 #include "k_estimate_batch.hpp"
 #include "k_consensus_batch.hpp"
+#include "k_match_window_batch.hpp"
 
 using namespace siftk;
 
@@ -85,6 +87,9 @@ struct siftmi_matcher {
     int64_t cap_mb_host = 0, cap_mb_tab = 0;
     int *mb_ints = nullptr;
     int64_t cap_mb_ints = 0;
+    // windowed batch matching (siftmi_match_window_batch) has no buffer of its own: its integer scratch (extents, histograms, scans,
+    // work counts) lies in w_cells, its work list, dense copy and order in w_work, w_desc, w_meta and w_order, its tables in mb_host
+    // and mb_tab, the dense results, sums and offsets in mb_ints; `nearest` and, for a host result, `pairs` are the ones above
     // segmented fit and median (siftmi_match_fit_batch / siftmi_match_shift_batch): the tables in pinned host memory (followed by the
     // per-segment results, which come back there) and on the device, the fit's partials and results, the median's results; on
     // demand.  Lists, pairs, mask, positions, keys and keep bytes are staged in the buffers of the single calls above
@@ -984,6 +989,233 @@ int siftmi_match_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1
     }
     launch_mb_partial(m->stream, (int)zf.work, d1, d2, (const MbWork *)(m->mb_tab + o_wf), m->partial);
     launch_mb_merge(m->stream, Ef, m->partial, blocks_f, ratio_th, dense, sums, mutual ? m->nearest : nullptr, nullptr);
+    launch_mb_scan(m->stream, sums, Ef, offs, (const int *)(m->mb_tab + o_sb), S, seg_off);
+    launch_mb_scatter(m->stream, Ef, dense, offs, blocks_f, result);
+    hipEventRecord(m->eb, m->stream);
+    HIPCHK(hipMemcpyAsync(seg_off_host, seg_off, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (!pairs_is_device) {
+        // the number of pairs is not known before the one wait: every row a query could have filled comes back
+        if (prof) hipEventRecord(m->ev[3], m->stream);
+        HIPCHK(hipMemcpyAsync(pairs, m->pairs, (size_t)NQ * sizeof(int2), hipMemcpyDeviceToHost, m->stream));
+        if (prof) hipEventRecord(m->ev[4], m->stream);
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipGetLastError());
+    hipEventElapsedTime(&m->last_ms, m->ea, m->eb);
+    if (prof) {
+        m->stage_ms[2] = m->last_ms;
+        if (!kp1_is_device) hipEventElapsedTime(&m->stage_ms[0], m->ev[0], m->ev[1]);
+        if (!kp2_is_device) hipEventElapsedTime(&m->stage_ms[1], m->ev[1], m->ev[2]);
+        if (!pairs_is_device) hipEventElapsedTime(&m->stage_ms[3], m->ev[3], m->ev[4]);
+    }
+    for (int s = 0; s < S; s++) pair_counts[s] = seg_off_host[s + 1] - seg_off_host[s];
+    return SIFTMI_OK;
+}
+
+// The windowed matcher over a batch of segment pairs (k_match_window_batch.hpp; the contract is DESIGN.md section 7 row 16)
+namespace {
+// cells per axis of a list of n records at most: the largest g <= grid_max with g * g <= max(1, n)
+int mwb_gcap(int64_t n, int grid_max) {
+    int g = (int)std::sqrt((double)(n > 1 ? n : 1));
+    while ((int64_t)g * g > n && g > 1) g--;
+    while ((int64_t)(g + 1) * (g + 1) <= n) g++;
+    return g < 1 ? 1 : g > grid_max ? grid_max : g;
+}
+// what one direction needs: rows are S + 1; cells: words of each of the four cell arrays; order / dense: entries of the queries'
+// order and records of the dense copy; work: the bound on the work items; lblocks / qblocks: entries of the two block tables
+struct MwbSizes { int64_t cells, order, dense, work, lblocks, qblocks; int live; };
+// The tables of one direction (null pointers: the sizes only).  A segment with an empty side is dead: no block, no cell, no work.
+// With a shared list (l.counts == NULL) row S bins it once; its grid is capped by the mean number of queries of a live segment as
+// well, so that the S query-side copies of its cells stay within the records of the batch.
+MwbSizes mwb_fill(const MbSide &q, const MbSide &l, int S, int grid_max, const float *shifts, const int *seg_block, MwbSeg *rows,
+                  int2 *lblocks, int2 *qblocks) {
+    MwbSizes z = {0, 0, 0, 0, 0, 0, 0};
+    int64_t nq_live = 0;
+    for (int s = 0; s < S; s++) if (mb_count(q, s) > 0 && mb_count(l, s) > 0) { z.live++; nq_live += mb_count(q, s); }
+    const bool shared = !l.counts;
+    int g_shared = 1;
+    if (rows) std::memset(rows, 0, (size_t)(S + 1) * sizeof(MwbSeg));
+    if (shared && z.live) {
+        const int64_t mean = nq_live / z.live > 1 ? nq_live / z.live : 1;
+        g_shared = mwb_gcap(l.shared < mean ? l.shared : mean, grid_max);
+        if (rows) { MwbSeg &r = rows[S]; r.l_count = (int)l.shared; r.ext = S; r.g_cap = g_shared; r.own_list = 1; }
+        for (int64_t c = 0; c * 256 < l.shared; c++, z.lblocks++) if (lblocks) lblocks[z.lblocks] = make_int2(S, (int)c);
+        z.cells += (int64_t)g_shared * g_shared + 1;
+        z.dense = l.shared;
+    }
+    int64_t qoff = 0, loff = 0;
+    for (int s = 0; s < S; s++) {
+        const int64_t nq = mb_count(q, s), nl = mb_count(l, s);
+        if (rows) { rows[s].ext = s; rows[s].g_cap = 1; }
+        if (nq > 0 && nl > 0) {
+            const int g = shared ? g_shared : mwb_gcap(nl, grid_max);
+            const int64_t cells = (int64_t)g * g;
+            if (rows) {
+                MwbSeg &r = rows[s];
+                r.q_first = (int)qoff; r.q_count = (int)nq; r.l_first = shared ? 0 : (int)loff; r.l_count = (int)nl;
+                r.q_cells = (int)z.cells; r.l_cells = shared ? 0 : (int)z.cells;
+                r.ext = shared ? S : s; r.g_cap = g; r.order = (int)z.order; r.dense = shared ? 0 : (int)z.dense;
+                r.out = seg_block ? seg_block[s] * SIFT_MB_QBLOCK : 0; r.own_list = !shared;
+                r.sx = shifts[2 * s]; r.sy = shifts[2 * s + 1];
+            }
+            for (int64_t c = 0; c * 256 < nq; c++, z.qblocks++) if (qblocks) qblocks[z.qblocks] = make_int2(s, (int)c);
+            if (!shared) {
+                for (int64_t c = 0; c * 256 < nl; c++, z.lblocks++) if (lblocks) lblocks[z.lblocks] = make_int2(s, (int)c);
+                z.dense += nl;
+            }
+            z.cells += cells + 1;
+            z.order += nq;
+            z.work += nq / SIFT_MW_QB + (nq < cells ? nq : cells) + 1;     // mw_work_cap's bound with the segment's cells
+        }
+        if (q.counts) qoff += nq;
+        if (l.counts) loff += nl;
+    }
+    return z;
+}
+// the blocks of the compaction: mb_fill's for the first side, `stride` the length of the segment's second list and `nparts` whether
+// the segment has work
+void mwb_fill_blocks(const MbSide &q, const MbSide &l, int S, MbBlock *blocks, int *seg_block) {
+    int64_t qoff = 0, loff = 0, e = 0;
+    for (int s = 0; s < S; s++) {
+        const int64_t nq = mb_count(q, s), nl = mb_count(l, s);
+        seg_block[s] = (int)e;
+        for (int64_t b0 = 0; b0 < nq; b0 += SIFT_MB_QBLOCK) {
+            const int qc = (int)(nq - b0 < SIFT_MB_QBLOCK ? nq - b0 : SIFT_MB_QBLOCK);
+            blocks[e++] = {qc, 0, (int)nl, nl > 0 ? 1 : 0, (int)b0, (int)loff, (int)(qoff + b0), 0};
+        }
+        if (q.counts) qoff += nq;
+        if (l.counts) loff += nl;
+    }
+    seg_block[S] = (int)e;
+}
+// the integer scratch of one direction inside w_cells: [ext_max | cnt_l | cnt_q] are zeroed together, ext_min starts at 0xff..
+struct MwbInts { int64_t ext_max, cnt_l, cnt_q, ext_min, start_l, start_q, n_work, w_off, spare, total; };
+MwbInts mwb_ints(int S, int64_t cells) {
+    MwbInts o;
+    const int64_t R = S + 1;
+    o.ext_max = 0; o.cnt_l = 2 * R; o.cnt_q = o.cnt_l + cells; o.ext_min = o.cnt_q + cells; o.start_l = o.ext_min + 2 * R;
+    o.start_q = o.start_l + cells; o.n_work = o.start_q + cells; o.w_off = o.n_work + R; o.spare = o.w_off + R + 1; o.total = o.spare + 1;
+    return o;
+}
+// one direction: the grids of all rows, the compacted work list and the scan.  nearest == null: dense gets `best` or -1 per query
+int mwb_direction(siftmi_matcher *m, int S, const MwbSizes &z, const MwbSeg *rows, const int2 *lblocks, const int2 *qblocks, const int *zero,
+                  const uint8_t *dq, const uint8_t *dl, int reverse, float wx, float wy, float ratio_th, int *dense, int *nearest) {
+    const MwbInts o = mwb_ints(S, z.cells);
+    int *w = m->w_cells;
+    uint32_t *ext_min = (uint32_t *)(w + o.ext_min), *ext_max = (uint32_t *)(w + o.ext_max);
+    hipStream_t st = m->stream;
+    HIPCHK(hipMemsetAsync(w + o.ext_max, 0, (size_t)(o.ext_min - o.ext_max) * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(w + o.ext_min, 0xff, (size_t)(2 * (S + 1)) * sizeof(int), st));
+    const dim3 bl((unsigned)z.lblocks), bq((unsigned)z.qblocks), th(256);
+    hipLaunchKernelGGL(mwb_extent_kernel, bl, th, 0, st, dl, rows, lblocks, ext_min, ext_max);
+    hipLaunchKernelGGL(mwb_count_kernel, bl, th, 0, st, dl, rows, lblocks, 1, reverse, (const uint32_t *)ext_min, (const uint32_t *)ext_max, wx, wy, w + o.cnt_l);
+    hipLaunchKernelGGL(mwb_count_kernel, bq, th, 0, st, dq, rows, qblocks, 0, reverse, (const uint32_t *)ext_min, (const uint32_t *)ext_max, wx, wy, w + o.cnt_q);
+    hipLaunchKernelGGL(mwb_scan_kernel, dim3((unsigned)(S + 1)), dim3(SIFT_MWB_SCAN_THREADS), 0, st, rows, (const uint32_t *)ext_min,
+                       (const uint32_t *)ext_max, wx, wy, w + o.cnt_l, w + o.cnt_q, w + o.start_l, w + o.start_q, w + o.n_work);
+    // w_off[s] = work items of the rows before s; w_off[S]: all of them (`zero` is a table word that holds 0: no segment values)
+    launch_mb_scan(st, w + o.n_work, S, w + o.w_off, zero, 0, w + o.spare);
+    hipLaunchKernelGGL(mwb_work_kernel, dim3((unsigned)S), dim3(SIFT_MWB_SCAN_THREADS), 0, st, rows, (const uint32_t *)ext_min,
+                       (const uint32_t *)ext_max, wx, wy, (const int *)(w + o.start_q), (const int *)(w + o.w_off), m->w_work, (int)z.work);
+    hipLaunchKernelGGL(mwb_scatter_list_kernel, bl, th, 0, st, dl, rows, lblocks, (const uint32_t *)ext_min, (const uint32_t *)ext_max, wx, wy,
+                       w + o.cnt_l, m->w_desc, m->w_meta);
+    hipLaunchKernelGGL(mwb_scatter_query_kernel, bq, th, 0, st, dq, rows, qblocks, reverse, (const uint32_t *)ext_min, (const uint32_t *)ext_max,
+                       wx, wy, w + o.cnt_q, m->w_order);
+    hipLaunchKernelGGL(mwb_match_kernel, dim3((unsigned)z.work), th, 0, st, dq, rows, (const uint32_t *)ext_min, (const uint32_t *)ext_max, wx, wy,
+                       reverse, (const int *)(w + o.start_l), (const int *)(w + o.start_q), (const int *)m->w_order, (const int2 *)m->w_work,
+                       (const int *)(w + o.w_off + S), (const uint4 *)m->w_desc, (const float4 *)m->w_meta, ratio_th, dense, nearest);
+    return SIFTMI_OK;
+}
+}  // namespace
+
+int siftmi_match_window_batch(siftmi_matcher *m, const siftmi_keypoint *kp1, int64_t n1, int32_t kp1_is_device,
+                              const siftmi_keypoint *kp2, int64_t n2, int32_t kp2_is_device, int32_t n_segments,
+                              const int64_t *counts1, const int64_t *counts2, float ratio_th, float wx, float wy, const float *shifts,
+                              int32_t mutual, int32_t grid_max, int32_t *pairs, int32_t pairs_is_device, int64_t *pair_counts) {
+    if (!m) return fail(SIFTMI_EINVAL, "null argument");
+    if (n_segments < 0 || n_segments > SIFT_MB_MAX_SEGMENTS) return fail(SIFTMI_EINVAL, "n_segments %d outside 0..%d", n_segments, SIFT_MB_MAX_SEGMENTS);
+    if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff / 8 || n2 > 0x7fffffff / 8) return fail(SIFTMI_EINVAL, "bad list size");
+    if ((n1 > 0 && !kp1) || (n2 > 0 && !kp2)) return fail(SIFTMI_EINVAL, "null keypoint list");
+    if (n_segments > 0 && (!counts2 || !pair_counts || !shifts)) return fail(SIFTMI_EINVAL, "null counts2, shifts or pair_counts with %d segments", n_segments);
+    if (!(ratio_th <= 1.0f)) return fail(SIFTMI_EINVAL, "ratio_th must be <= 1, not %g", ratio_th);
+    if (!(wx >= 0.f) || !(wy >= 0.f)) return fail(SIFTMI_EINVAL, "the window must be >= 0 (it may be infinite), not (%g, %g)", wx, wy);
+    if (grid_max < 0 || grid_max > SIFT_MW_MAXG) return fail(SIFTMI_EINVAL, "grid_max must be 0 .. %d, not %d", SIFT_MW_MAXG, grid_max);
+    const int S = n_segments;
+    int64_t sum1 = 0, sum2 = 0;
+    for (int s = 0; s < S; s++) {
+        if (counts2[s] < 0 || (counts1 && counts1[s] < 0)) return fail(SIFTMI_EINVAL, "negative count in segment %d", s);
+        if (counts2[s] > n2 || (counts1 && counts1[s] > n1)) return fail(SIFTMI_EINVAL, "the count of segment %d exceeds its list", s);
+        if (!std::isfinite(shifts[2 * s]) || !std::isfinite(shifts[2 * s + 1]))
+            return fail(SIFTMI_EINVAL, "the window shift of segment %d must be finite, not (%g, %g)", s, shifts[2 * s], shifts[2 * s + 1]);
+        sum2 += counts2[s]; sum1 += counts1 ? counts1[s] : 0;
+    }
+    if (sum2 != n2) return fail(SIFTMI_EINVAL, "counts2 add up to %lld, the second list has %lld records", (long long)sum2, (long long)n2);
+    if (counts1 && sum1 != n1) return fail(SIFTMI_EINVAL, "counts1 add up to %lld, the first list has %lld records", (long long)sum1, (long long)n1);
+    const int64_t NQ = counts1 ? n1 : (int64_t)S * n1;         // queries of the concatenated first side: the capacity of `pairs`
+    if (NQ > 0x7fffffff / 8) return fail(SIFTMI_EINVAL, "%lld queries in all: more than 2^28 - 1", (long long)NQ);
+    HIPCHK(hipSetDevice(m->device));
+    for (float &v : m->stage_ms) v = -1.f;
+    m->last_ms = 0;
+    for (int s = 0; s < S; s++) pair_counts[s] = 0;
+    const MbSide side1 = {counts1, n1}, side2 = {counts2, n2};
+    const int G = grid_max ? grid_max : SIFT_MW_MAXG;
+    const MwbSizes zf = mwb_fill(side1, side2, S, G, shifts, nullptr, nullptr, nullptr, nullptr);
+    if (zf.live == 0) return SIFTMI_OK;                        // no segment with an element on both sides: no pair, nothing is launched
+    if (!pairs) return fail(SIFTMI_EINVAL, "null pairs buffer");
+    const MwbSizes zr = mutual ? mwb_fill(side2, side1, S, G, shifts, nullptr, nullptr, nullptr, nullptr) : MwbSizes{0, 0, 0, 0, 0, 0, 0};
+    int64_t Ef64 = 0;
+    for (int s = 0; s < S; s++) Ef64 += mb_qblocks(mb_count(side1, s));
+    const int64_t lim = (int64_t)1 << 30;
+    if (zf.work > lim || zr.work > lim || zf.cells > lim / 4 || zr.cells > lim / 4 || Ef64 * SIFT_MB_QBLOCK > 0x7fffffff)
+        return fail(SIFTMI_EINVAL, "the batch is too large: %lld + %lld work items, %lld + %lld cells", (long long)zf.work, (long long)zr.work,
+                    (long long)zf.cells, (long long)zr.cells);
+    const int Ef = (int)Ef64;
+    // the tables, one upload: rows forward / reverse, the blocks of the compaction, the block tables, the segments' first blocks
+    const int64_t R = S + 1;
+    const int64_t o_rf = 0, o_rr = o_rf + R * (int64_t)sizeof(MwbSeg), o_bf = o_rr + (mutual ? R : 0) * (int64_t)sizeof(MwbSeg),
+                  o_lf = o_bf + Ef * (int64_t)sizeof(MbBlock), o_qf = o_lf + zf.lblocks * (int64_t)sizeof(int2),
+                  o_lr = o_qf + zf.qblocks * (int64_t)sizeof(int2), o_qr = o_lr + zr.lblocks * (int64_t)sizeof(int2),
+                  o_sb = o_qr + zr.qblocks * (int64_t)sizeof(int2), o_zero = o_sb + R * (int64_t)sizeof(int),
+                  tab_bytes = o_zero + (int64_t)sizeof(int);
+    const int64_t i_sums = 0, i_offs = i_sums + Ef, i_seg = i_offs + Ef + 1, i_dense = (i_seg + S + 1 + 1) / 2 * 2, n_ints = i_dense + (int64_t)Ef * SIFT_MB_QBLOCK;
+    const int64_t w_ints = std::max(mwb_ints(S, zf.cells).total, mwb_ints(S, zr.cells).total);
+    const int64_t n_work = std::max(zf.work, zr.work), n_dense = std::max(zf.dense, zr.dense), n_order = std::max(zf.order, zr.order);
+    int rc;
+    if ((rc = ensure_pinned(&m->mb_host, &m->cap_mb_host, tab_bytes + R * (int64_t)sizeof(int))) ||
+        (rc = ensure((void **)&m->mb_tab, &m->cap_mb_tab, tab_bytes, 1)) ||
+        (rc = ensure((void **)&m->mb_ints, &m->cap_mb_ints, n_ints, sizeof(int))) ||
+        (rc = ensure((void **)&m->w_cells, &m->cap_w_cells, w_ints, sizeof(int))) ||
+        (rc = ensure((void **)&m->w_work, &m->cap_w_work, n_work, sizeof(int2))) ||
+        (rc = ensure((void **)&m->w_desc, &m->cap_w_desc, n_dense * 8, sizeof(uint4))) ||
+        (rc = ensure((void **)&m->w_meta, &m->cap_w_meta, n_dense, sizeof(float4))) ||
+        (rc = ensure((void **)&m->w_order, &m->cap_w_order, n_order, sizeof(int)))) return rc;
+    if (mutual && (rc = ensure((void **)&m->nearest, &m->cap_nearest, n2, sizeof(int)))) return rc;
+    if (!pairs_is_device && (rc = ensure((void **)&m->pairs, &m->cap_pairs, NQ, sizeof(int2)))) return rc;
+    int *seg_block = (int *)(m->mb_host + o_sb);
+    mwb_fill_blocks(side1, side2, S, (MbBlock *)(m->mb_host + o_bf), seg_block);
+    *(int *)(m->mb_host + o_zero) = 0;
+    mwb_fill(side1, side2, S, G, shifts, seg_block, (MwbSeg *)(m->mb_host + o_rf), (int2 *)(m->mb_host + o_lf), (int2 *)(m->mb_host + o_qf));
+    if (mutual) mwb_fill(side2, side1, S, G, shifts, nullptr, (MwbSeg *)(m->mb_host + o_rr), (int2 *)(m->mb_host + o_lr), (int2 *)(m->mb_host + o_qr));
+    int *seg_off_host = (int *)(m->mb_host + tab_bytes);
+    if (kp1_is_device || kp2_is_device || pairs_is_device) HIPCHK(hipDeviceSynchronize());
+    const uint8_t *d1 = (const uint8_t *)kp1, *d2 = (const uint8_t *)kp2;
+    const bool prof = m->profile && m->ev[0];
+    if (prof) hipEventRecord(m->ev[0], m->stream);
+    if (!kp1_is_device && (rc = stage_list(m, &m->kp1, &m->cap1, kp1, n1, &d1))) return rc;
+    if (prof) hipEventRecord(m->ev[1], m->stream);
+    if (!kp2_is_device && (rc = stage_list(m, &m->kp2, &m->cap2, kp2, n2, &d2))) return rc;
+    if (prof) hipEventRecord(m->ev[2], m->stream);
+    HIPCHK(hipMemcpyAsync(m->mb_tab, m->mb_host, (size_t)tab_bytes, hipMemcpyHostToDevice, m->stream));
+    int *sums = m->mb_ints + i_sums, *offs = m->mb_ints + i_offs, *seg_off = m->mb_ints + i_seg, *dense = m->mb_ints + i_dense;
+    const MbBlock *blocks_f = (const MbBlock *)(m->mb_tab + o_bf);
+    const int *zero = (const int *)(m->mb_tab + o_zero);
+    int2 *result = pairs_is_device ? (int2 *)pairs : m->pairs;
+    hipEventRecord(m->ea, m->stream);
+    // reverse scan: the nearest candidate among its segment's first list for every record of the second side (the shifts negated)
+    if (mutual && (rc = mwb_direction(m, S, zr, (const MwbSeg *)(m->mb_tab + o_rr), (const int2 *)(m->mb_tab + o_lr), (const int2 *)(m->mb_tab + o_qr),
+                                      zero, d2, d1, 1, wx, wy, ratio_th, nullptr, m->nearest))) return rc;
+    if ((rc = mwb_direction(m, S, zf, (const MwbSeg *)(m->mb_tab + o_rf), (const int2 *)(m->mb_tab + o_lf), (const int2 *)(m->mb_tab + o_qf),
+                            zero, d1, d2, 0, wx, wy, ratio_th, dense, nullptr))) return rc;
+    hipLaunchKernelGGL(mwb_finish_kernel, dim3((unsigned)Ef), dim3(256), 0, m->stream, blocks_f, dense, sums, mutual ? (const int *)m->nearest : (const int *)nullptr);
     launch_mb_scan(m->stream, sums, Ef, offs, (const int *)(m->mb_tab + o_sb), S, seg_off);
     launch_mb_scatter(m->stream, Ef, dense, offs, blocks_f, result);
     hipEventRecord(m->eb, m->stream);

@@ -441,6 +441,90 @@ class MatchPlan(object):
         total = int(pair_counts.sum())
         return (pairs[:total] if out == "device" else pairs[:total].copy()), pair_counts
 
+    BATCH_MAX_GRID = 256
+
+    def match_window_batch(self, kp1, counts1, kp2, counts2, window, window_shift=(0.0, 0.0), ratio=None, mutual=False, grid_max=0,
+                           out="host"):
+        """``match(kp1_s, kp2_s, raw_results=True, window=, window_shift=)`` for S segment pairs in one call: ``match_batch`` with
+        the windowed matcher, one set of launches and one synchronisation (extension).  The lists,
+        the counts, ``ratio``, ``mutual``, ``out`` and the result are ``match_batch``'s; keypoint j of segment s's second list is a
+        *candidate* of keypoint i of its first list iff ``abs((x2[j] - x1[i]) - sx_s) <= wx and abs((y2[j] - y1[i]) - sy_s) <= wy``
+        (float32, ``match(window=)``'s predicate), and the rule sees the candidates only.  Every list is binned on a grid of its
+        own, so a segment far away or with non-finite coordinates costs the others nothing; no record of another segment can
+        enter a segment's result.  As for ``match(window=)``: a keypoint without a candidate pairs with nothing, a keypoint with
+        exactly ONE candidate always pairs with it; ``mutual=True`` and ``consensus_batch`` are the filters for those.  (The
+        keywords live in a method of their own because ``match_batch``'s parameter list is pinned by the tests of row 12.)
+
+        :param kp1, counts1, kp2, counts2: as for ``match_batch`` (``counts1=None``: ONE first list for every segment)
+        :param window: the half width of the search window in pixels, a scalar or an ``(wx, wy)`` pair (x first; ``inf`` is allowed,
+                       negative or NaN is an error).  Required: without a window the call is ``match_batch``
+        :param window_shift: ``(sx, sy)``, the expected displacement of the second list against the first, for all segments, or an
+                       (S, 2) array with one shift per segment; finite
+        :param ratio: None (``par.MatchRatio``) or a number with ``ratio ** 2 <= 1``
+        :param mutual: keep (i, j) only if i is also the nearest candidate of j inside the segment
+        :param grid_max: 0 (the library chooses) or 1 .. 256, the most cells per axis of a segment's grid.  The result does not
+                       depend on it
+        :param out: ``"host"`` or ``"device"``, as for ``match_batch``
+        :return: ``(pairs, pair_counts)`` exactly as ``match_batch`` returns them: segments in order, ascending i inside a
+                 segment, indices local to the segment; they go straight into ``consensus_batch``, ``fit_batch`` and ``shift_batch``
+        """
+        if window is None:
+            raise ValueError("match_window_batch needs a window; without one the call is match_batch(kp1, counts1, kp2, counts2)")
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        r = par.MatchRatio if ratio is None else ratio
+        th = numpy.float32(r * r)
+        if not th <= numpy.float32(1):
+            raise ValueError("ratio ** 2 must be <= 1, not %r" % (float(th),))
+        wx, wy = (numpy.float32(w) for w in (window if hasattr(window, "__len__") else (window, window)))
+        if not (wx >= 0 and wy >= 0):
+            raise ValueError("the window must be >= 0 (it may be infinite), not (%r, %r)" % (float(wx), float(wy)))
+        grid_max = int(grid_max)
+        if grid_max < 0 or grid_max > self.BATCH_MAX_GRID:
+            raise ValueError("grid_max must be 0 .. %d, not %d" % (self.BATCH_MAX_GRID, grid_max))
+        p1, dev1, n1, keep1 = self._records(kp1)
+        p2, dev2, n2, keep2 = self._records(kp2)
+        c2 = numpy.ascontiguousarray([int(c) for c in counts2], dtype=numpy.int64).reshape(-1)
+        S = len(c2)
+        c1 = None if counts1 is None else numpy.ascontiguousarray([int(c) for c in counts1], dtype=numpy.int64).reshape(-1)
+        if S > self.BATCH_MAX_SEGMENTS:
+            raise ValueError("%d segments: more than %d" % (S, self.BATCH_MAX_SEGMENTS))
+        if c1 is not None and len(c1) != S:
+            raise ValueError("counts1 has %d entries, counts2 %d" % (len(c1), S))
+        if (c2 < 0).any() or (c1 is not None and (c1 < 0).any()):
+            raise ValueError("negative count")
+        if int(c2.sum()) != n2 or (c1 is not None and int(c1.sum()) != n1):
+            raise ValueError("the counts do not add up to the lists: %s of %d and %d of %d records" %
+                             ("-" if c1 is None else int(c1.sum()), n1, int(c2.sum()), n2))
+        shifts = numpy.asarray(window_shift, dtype=numpy.float32)
+        if shifts.shape == (2,):
+            shifts = numpy.broadcast_to(shifts, (S, 2))
+        if shifts.shape != (S, 2):
+            raise ValueError("window_shift must be (sx, sy) or an (S, 2) array with S = %d, not of shape %r" % (S, shifts.shape))
+        shifts = numpy.ascontiguousarray(shifts, dtype=numpy.float32)
+        if not numpy.isfinite(shifts).all():
+            raise ValueError("the window shift must be finite")
+        rows = n1 * S if c1 is None else n1
+        pair_counts = numpy.zeros(S, numpy.int64)
+        if out == "device":
+            import torch
+            pairs = torch.empty((rows, 2), dtype=torch.int32, device=torch.device("cuda", self.device))
+            pp = pairs.data_ptr()
+        else:
+            pairs = numpy.empty((rows, 2), dtype=numpy.int32)
+            pp = pairs.ctypes.data
+        if S == 0:
+            return pairs[:0], pair_counts
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_match_window_batch(self._handle, p1, n1, dev1, p2, n2, dev2, S, None if c1 is None else c1.ctypes.data,
+                                                            c2.ctypes.data, C.c_float(th), C.c_float(wx), C.c_float(wy), shifts.ctypes.data,
+                                                            int(bool(mutual)), grid_max, pp if rows else None, int(out == "device"),
+                                                            pair_counts.ctypes.data))
+            if self.profile:
+                self.events += self._stage_events()
+        total = int(pair_counts.sum())
+        return (pairs[:total] if out == "device" else pairs[:total].copy()), pair_counts
+
     BATCH_MAX_WORK = 1 << 20
 
     def _estimate_batch_args(self, kp1, counts1, kp2, counts2, pairs, pair_counts, mask):
