@@ -70,11 +70,11 @@ def solve(pts, idx):
 def vote_matrix(pts, models, tol):
     """boolean (len(models), M): does match j vote for the model -- float32, every operation rounded on its own"""
     tol = np.float32(tol)
-    tol2 = tol * tol
     x0, y0, x1, y1 = (np.ascontiguousarray(pts[:, k]) for k in range(4))
     m = np.asarray(models, np.float32).reshape(-1, 6)
     a, b, c, d, e, f = (m[:, k:k + 1] for k in range(6))
     with np.errstate(all="ignore"):
+        tol2 = tol * tol                                # float32: inf from 1.9e19 on, 0 below 2.7e-23
         t = a * x0; u = b * y0; t += u; t += c; t -= x1; t *= t
         s = d * x0; u = e * y0; s += u; s += f; s -= y1; s *= s
         t += s

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import consensus_batch_ref as cb
+import consensus_cases as cc
 import consensus_ref as cr
 import estimate_batch_ref as eb
 import fit_ref as fr
@@ -112,8 +113,11 @@ def mp(siftlib):
 
 # ---------------------------------------------------------------------------------------------- 1. the crafted batches
 # n_hyp 1; 15: less than the 16 of the smallest chunk; 17: two chunks (9 + 8) below 2048 tiles and one chunk from 2048 tiles on
-# (many_batch); 520: above the 512 LDS counters, and with the 70 tiles of large_batch 29 chunks of 18 with a last one of 16; 2048
+# (many_batch); 520: above the 512 LDS counters, and with the 70 tiles of large_batch 29 chunks of 18 with a last one of 16; 2048.
+# consensus_cases.WIDE_BATCH_CASES: many_batch with 520, 1024 and 1025 hypotheses, chunks of 260, 512 and 342 -- a workgroup's fold
+# of its LDS counters takes a second trip
 CASES = [(name, H) for name in ("edge", "leak", "tile") for H in (1, 15, 17, 520, 2048)] + [("large", 17), ("large", 520), ("many", 17)]
+CASES += [(name, H) for name, H, _ in cc.WIDE_BATCH_CASES]
 
 
 @pytest.mark.parametrize("form", ["separate", "shared"])
