@@ -254,6 +254,42 @@ int siftmi_batch_transform(siftmi_batch *batch, const void *const *images, int32
                            const float *maps /* n x 6: matrix[4], offset[2] */, const float *fills /* n */,
                            int32_t mode, double *kernel_ms);
 int siftmi_batch_minmax(const siftmi_batch *batch, float *mins, float *maxs, int32_t n_images);
+/* What a stack is aligned for (extension; DESIGN.md section 7 row 17, restated in numpy by tests/stack_ref.py; the reference
+ * leaves combining the aligned frames to its caller):
+ * siftmi_batch_stack      warps n float32 frames of the batch's H x W as siftmi_batch_transform does and reduces them to ONE
+ *                         OH x OW plane in the same launch (stack_reduce_kernel / stack_median_kernel, csrc/k_stack.hpp); the n
+ *                         warped planes are never written.  Per output pixel, binary32 with one rounding per operation:
+ *                           v_s     the value siftmi_batch_transform writes for frame s at this pixel
+ *                           live_s  0 <= tx && tx < W + -0.5f && 0 <= ty && ty < H + -0.5f for the source point (ty, tx) of
+ *                                   siftmi_plan_transform: where v_s is not fills[s] for a geometric reason.  A non-finite tx or
+ *                                   ty is never live: a map with a NaN leaves its frame out wherever the NaN reaches (an all-NaN
+ *                                   map: everywhere, which is what LinearAlign.align_batch gives a frame without a usable pair)
+ *                           c       the number of live frames, written to `coverage`
+ *                           SUM     over the live frames in ascending s: acc = v for the first, acc = acc + v for each later one
+ *                           MEAN    acc / (float)c
+ *                           MEDIAN  with key(v) = bits(v) ^ (bits(v) >> 31 ? 0xffffffff : 0x80000000) (ascending key = the total
+ *                                   order of float32, NaNs by their bits, as for siftmi_match_shift) and lo, hi the live values of
+ *                                   rank (c - 1) >> 1 and c >> 1: lo when c is odd, (lo + hi) * 0.5f when even; n <= 64 only.  (A
+ *                                   NaN the warp's own arithmetic creates -- 0 * inf, inf - inf -- is the device's default NaN,
+ *                                   a positive one: it sorts above +inf)
+ *                           c == 0  `empty`
+ *   images, maps, fills, mode   as for siftmi_batch_transform (float32 frames only; host frames staged the same way)
+ *   out          OH x OW float32, host (staged in a buffer the batch owns and grows, with the coverage behind it) or device
+ *   coverage     OH x OW int32 where `out` lives, or NULL
+ *   kernel_ms    optional, hipEvent duration of the launch (0 when nothing is launched)
+ * One launch, one synchronisation; device pointers are ordered after the NULL stream as everywhere.  An empty output launches
+ * nothing and returns 0.  n_images == 0 with a non-empty output fills `out` with `empty` and `coverage` with 0: the reduction
+ * kernel launched over no frame is the fill.  SIFTMI_EINVAL, nothing launched: a null handle, a null table or output with work
+ * to do, a null frame, a batch created for RGB8, an unknown `reduce`, SIFTMI_STACK_MEDIAN with n_images > 64, a negative shape
+ * or count, n_images > 65535, out_height > 262140. */
+#define SIFTMI_STACK_SUM 0
+#define SIFTMI_STACK_MEAN 1
+#define SIFTMI_STACK_MEDIAN 2
+#define SIFTMI_STACK_MEDIAN_MAX 64
+int siftmi_batch_stack(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
+                       float *out /* OH x OW */, int32_t *coverage /* OH x OW, may be null */, int32_t out_is_device,
+                       int32_t out_width, int32_t out_height, const float *maps /* n x 6 */, const float *fills /* n */,
+                       int32_t mode, int32_t reduce, float empty, double *kernel_ms);
 
 /* ---- MatchPlan -----------------------------------------------------------------------------
  * siftmi_match_create <- MatchPlan.__init__ (match.py:77-139)

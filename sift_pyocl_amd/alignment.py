@@ -112,6 +112,7 @@ class LinearAlign(object):
         self.sem = threading.Semaphore()
         self.relative_transfo = None
         self.last_transform_ms = 0.0
+        self.last_stack_ms = 0.0
         self._ref_dev = None
         self._set_reference(self.sift.keypoints(image))
 
@@ -518,68 +519,133 @@ class LinearAlign(object):
             ref, None, records, counts, window=max_shift, window_shift=shift, ratio=match_ratio, out="device"),
             shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes)
 
-    def _align_batch(self, images, matcher, shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes):
-        """the body of ``align_batch``; ``matcher(ref_list, records, counts)`` returns ``(pairs, pair_counts)`` with the pairs on
-        the device"""
+    def stack(self, images, reduce="mean", max_shift=None, expected_shift=None, shift_only=False, robust=False, robust_tol=3.0,
+              robust_hyp=2048, match_ratio=None, empty=numpy.nan, return_all=False, out="host", lanes=None):
+        """Align a stack of S frames on the reference image and combine them into ONE image (extension; DESIGN.md section 7 row
+        17): the estimate of every frame is ``align_batch``'s (``align_batch_window``'s when ``max_shift`` is given), and the warp
+        is ``BatchPlan.stack_batch``, which reduces the S warped frames pixel by pixel in the launch that samples them -- the
+        aligned planes are never written and only the result crosses the link.  Greyscale aligners only.
+
+        A pixel of the result combines the frames that cover it: those whose warped value there is not the fill.  ``"mean"`` and
+        ``"sum"`` add them in the order of the stack; ``"median"`` (at most 64 frames) drops what only a few frames show --
+        zingers, cosmic rays, a passing object.  A frame without a usable pair (mode 0) has an all-NaN map: it covers nothing, is
+        left out everywhere, and still gets ``align_batch``'s warning.  The reference image takes part only if the caller puts it
+        into `images`.
+
+        :param images: as for ``align_batch``
+        :param reduce: ``"mean"``, ``"sum"`` or ``"median"``
+        :param max_shift, expected_shift: None for ``align_batch``'s matcher; otherwise the window of ``align_batch_window``
+        :param shift_only, robust, robust_tol, robust_hyp, match_ratio, lanes: as for ``align_batch``
+        :param empty: the value of a pixel that no frame covers
+        :param return_all: return ``align_batch``'s dict without ``result`` and with ``stack``, the (OH, OW) float32 image, and
+                       ``coverage``, the (OH, OW) int32 number of frames that cover each pixel
+        :param out: ``"host"``: numpy arrays; ``"device"``: torch tensors on the aligner's device
+        :return: the combined image (OH, OW), or the dict
+        """
+        if self.RGB:
+            raise RuntimeError("stack combines float32 frames; an RGB aligner has no stack reduction")
+        from .batch import BatchPlan
+        if reduce not in BatchPlan.STACK_REDUCERS:
+            raise ValueError("reduce must be one of %s, not %r" % (sorted(BatchPlan.STACK_REDUCERS), reduce))
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        if max_shift is None:
+            if expected_shift is not None:
+                raise ValueError("expected_shift needs max_shift")
+            matcher = lambda ref, records, counts: self.match.match_batch(ref, None, records, counts, ratio=match_ratio, out="device")  # noqa: E731
+        else:
+            shift = (0.0, 0.0) if expected_shift is None else expected_shift
+            matcher = lambda ref, records, counts: self.match.match_window_batch(      # noqa: E731
+                ref, None, records, counts, window=max_shift, window_shift=shift, ratio=match_ratio, out="device")
+        with self.sem:
+            bp = self._batch_plan(lanes)
+            frames, matrix, offset, mode, fills, rest = self._estimate_batch(bp, images, matcher, shift_only, robust, robust_tol, robust_hyp)
+            plane, cover = bp.stack_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, reduce=reduce, empty=empty,
+                                          coverage=True, out=out)
+            self.last_stack_ms = bp.last_stack_ms
+            if self.profile:
+                self.events.append(("stack_batch", StageEvent(bp.last_stack_ms)))
+            if not return_all:
+                return plane
+            res = {"stack": plane, "coverage": cover}
+            res.update(rest())
+            return res
+
+    def _estimate_batch(self, bp, images, matcher, shift_only, robust, robust_tol, robust_hyp):
+        """The estimate of every frame of a stack, shared by ``align_batch`` and ``stack`` (called with the semaphore held):
+        ``(frames, matrix, offset, mode, fills, rest)`` -- the device frames, the (S, 2, 2) / (S, 2) maps (all NaN for a frame
+        without a usable pair, which is warned about here), the (S,) int8 modes, the fill values, and ``rest()``, which builds
+        the other entries of the ``return_all`` dict."""
         import torch
+        frames = self._device_frames(images)
+        S = len(frames)
+        ref_list = self.ref_kp if self._ref_dev is None else self._ref_dev
+        counts, records = bp.keypoints_batch_device(frames)
+        fills = bp.minmax_batch()[0]
+        counts = numpy.asarray(counts, numpy.int64).reshape(S)
+        dev = torch.device("cuda", self.device)
+        if self.ref_kp.size and int(counts.sum()):
+            pairs, pc = matcher(ref_list, records, counts)
+        else:
+            pairs, pc = torch.empty((0, 2), dtype=torch.int32, device=dev), numpy.zeros(S, numpy.int64)
+        starts = numpy.concatenate([[0], numpy.cumsum(pc)]).astype(numpy.int64)
+        lists = (ref_list, None, records, counts, pairs, pc)
+        matched = int(pc.sum()) > 0
+        mask = None
+        if robust and matched:
+            mask, winners = self.match.consensus_batch(*lists, n_hyp=robust_hyp, tol=robust_tol, seed=0, out="device")[:2]
+            for s in numpy.nonzero(numpy.isnan(winners).any(axis=1) & (pc > 0))[0]:
+                logger.warning("No consensus among %s matches of frame %d: all of them are used" % (pc[s], s))
+                mask[int(starts[s]):int(starts[s + 1])] = 1
+        matrix = numpy.full((S, 2, 2), numpy.nan, numpy.float32)
+        offset = numpy.full((S, 2), numpy.nan, numpy.float32)
+        mode = numpy.zeros(S, numpy.int8)
+        used = numpy.zeros(S, numpy.int64)
+        rms = numpy.full(S, numpy.nan, numpy.float64)
+        affine = numpy.zeros(S, bool)
+        if matched and not shift_only:
+            models, fit_rms, n_fit = self.match.fit_batch(*lists, mask=mask)
+            affine = numpy.isfinite(models).all(axis=1) & (n_fit >= MIN_MATCHES_AFFINE)
+            a, b, c, d, e, f = (models[affine, k] for k in range(6))
+            matrix[affine] = numpy.stack([e, d, b, a], axis=1).reshape(-1, 2, 2).astype(numpy.float32)
+            offset[affine] = numpy.stack([f, c], axis=1).astype(numpy.float32)
+            mode[affine], used[affine], rms[affine] = 2, n_fit[affine], fit_rms[affine]
+        if matched and (~affine & (pc > 0)).any():
+            moved, n_moved = self.match.shift_batch(*lists, mask=mask)
+            shifted = ~affine & (n_moved > 0)
+            matrix[shifted] = numpy.identity(2, dtype=numpy.float32)
+            offset[shifted] = moved[shifted][:, ::-1]                    # (dx, dy) -> the kernel's (y, x) order
+            mode[shifted], used[shifted] = 1, n_moved[shifted]
+        for s in numpy.nonzero(mode == 0)[0]:
+            logger.warning("No matching keypoints in frame %d: its plane is the fill value" % s)
+
+        def rest():
+            host = records.cpu().numpy()
+            ends = numpy.cumsum(counts) * 144
+            keypoint = [host[int(e - 144 * n):int(e)].copy().view(SiftPlan.dtype_kp).view(numpy.recarray) for e, n in zip(ends, counts)]
+            res = {"matrix": matrix, "offset": offset, "mode": mode, "n": used, "rms": rms, "fill": fills,
+                   "counts": counts, "keypoint": keypoint, "pairs": pairs.cpu().numpy(), "pair_counts": pc}
+            if robust:
+                res["inliers"] = mask.cpu().numpy().astype(bool) if mask is not None else numpy.zeros(0, bool)
+            return res
+        return frames, matrix, offset, mode, fills, rest
+
+    def _align_batch(self, images, matcher, shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes):
+        """the body of ``align_batch``: the estimate of every frame, then the warp; ``matcher(ref_list, records, counts)`` returns
+        ``(pairs, pair_counts)`` with the pairs on the device"""
         if out not in ("host", "device"):
             raise ValueError("out must be 'host' or 'device', not %r" % (out,))
         with self.sem:
             bp = self._batch_plan(lanes)
-            frames = self._device_frames(images)
-            S = len(frames)
-            ref_list = self.ref_kp if self._ref_dev is None else self._ref_dev
-            counts, records = bp.keypoints_batch_device(frames)
-            fills = bp.minmax_batch()[0]
-            counts = numpy.asarray(counts, numpy.int64).reshape(S)
-            dev = torch.device("cuda", self.device)
-            if self.ref_kp.size and int(counts.sum()):
-                pairs, pc = matcher(ref_list, records, counts)
-            else:
-                pairs, pc = torch.empty((0, 2), dtype=torch.int32, device=dev), numpy.zeros(S, numpy.int64)
-            starts = numpy.concatenate([[0], numpy.cumsum(pc)]).astype(numpy.int64)
-            lists = (ref_list, None, records, counts, pairs, pc)
-            matched = int(pc.sum()) > 0
-            mask = None
-            if robust and matched:
-                mask, winners = self.match.consensus_batch(*lists, n_hyp=robust_hyp, tol=robust_tol, seed=0, out="device")[:2]
-                for s in numpy.nonzero(numpy.isnan(winners).any(axis=1) & (pc > 0))[0]:
-                    logger.warning("No consensus among %s matches of frame %d: all of them are used" % (pc[s], s))
-                    mask[int(starts[s]):int(starts[s + 1])] = 1
-            matrix = numpy.full((S, 2, 2), numpy.nan, numpy.float32)
-            offset = numpy.full((S, 2), numpy.nan, numpy.float32)
-            mode = numpy.zeros(S, numpy.int8)
-            used = numpy.zeros(S, numpy.int64)
-            rms = numpy.full(S, numpy.nan, numpy.float64)
-            affine = numpy.zeros(S, bool)
-            if matched and not shift_only:
-                models, fit_rms, n_fit = self.match.fit_batch(*lists, mask=mask)
-                affine = numpy.isfinite(models).all(axis=1) & (n_fit >= MIN_MATCHES_AFFINE)
-                a, b, c, d, e, f = (models[affine, k] for k in range(6))
-                matrix[affine] = numpy.stack([e, d, b, a], axis=1).reshape(-1, 2, 2).astype(numpy.float32)
-                offset[affine] = numpy.stack([f, c], axis=1).astype(numpy.float32)
-                mode[affine], used[affine], rms[affine] = 2, n_fit[affine], fit_rms[affine]
-            if matched and (~affine & (pc > 0)).any():
-                moved, n_moved = self.match.shift_batch(*lists, mask=mask)
-                shifted = ~affine & (n_moved > 0)
-                matrix[shifted] = numpy.identity(2, dtype=numpy.float32)
-                offset[shifted] = moved[shifted][:, ::-1]                    # (dx, dy) -> the kernel's (y, x) order
-                mode[shifted], used[shifted] = 1, n_moved[shifted]
-            for s in numpy.nonzero(mode == 0)[0]:
-                logger.warning("No matching keypoints in frame %d: its plane is the fill value" % s)
+            frames, matrix, offset, mode, fills, rest = self._estimate_batch(bp, images, matcher, shift_only, robust, robust_tol, robust_hyp)
             result = bp.transform_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, out=out)
             self.last_transform_ms = bp.last_transform_ms
             if self.profile:
                 self.events.append(("transform_batch", StageEvent(bp.last_transform_ms)))
             if not return_all:
                 return result
-            host = records.cpu().numpy()
-            ends = numpy.cumsum(counts) * 144
-            keypoint = [host[int(e - 144 * n):int(e)].copy().view(SiftPlan.dtype_kp).view(numpy.recarray) for e, n in zip(ends, counts)]
-            res = {"result": result, "matrix": matrix, "offset": offset, "mode": mode, "n": used, "rms": rms, "fill": fills,
-                   "counts": counts, "keypoint": keypoint, "pairs": pairs.cpu().numpy(), "pair_counts": pc}
-            if robust:
-                res["inliers"] = mask.cpu().numpy().astype(bool) if mask is not None else numpy.zeros(0, bool)
+            res = {"result": result}
+            res.update(rest())
             return res
 
     def log_profile(self):

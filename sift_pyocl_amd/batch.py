@@ -42,6 +42,7 @@ class BatchPlan(SiftPlan):
         self._records_per_frame = 4096.0
         self._batch_frames = None            # frames of the last finished batch (minmax_batch)
         self.last_transform_ms = 0.0
+        self.last_stack_ms = 0.0
         self._light = kwargs.get("profile") == "light"
         if kwargs.get("profile") and not self._light:
             raise RuntimeError("BatchPlan only supports profile='light' (blur brackets); profile a SiftPlan for per-stage events")
@@ -262,23 +263,9 @@ class BatchPlan(SiftPlan):
         # stack is one copy and separate arrays are one each -- a host-side numpy.stack costs more than the copies it saves)
         return ptrs, n, is_dev, keep
 
-    def transform_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, out="host"):
-        """Affine warp of S frames of the plan's shape in one launch (``siftmi_batch_transform``): frame s of the result is bit
-        for bit ``LinearAlign.transform(matrices[s], offsets[s], images[s], fills[s], mode)``.  One synchronisation, one upload of a
-        host stack (separate host arrays: one each) and one copy back of a host result.  A map with a non-finite entry gives ``fills[s]`` wherever it reaches
-        (all NaN: the whole plane).  Device memory: the result, plus the frames when they come from the host.
-
-        :param images: S frames, all numpy arrays or all device tensors, or one (S, H, W[, 3]) stack: float32 H x W, or uint8
-                       H x W x 3 for an RGB plan (nothing is converted)
-        :param matrices: (S, 2, 2) or (S, 4), acting on (y, x) as in ``LinearAlign.transform``
-        :param offsets: (S, 2)
-        :param fills: a scalar or (S,); for an RGB plan every value must lie in [0, 255]
-        :param out_shape: (OH, OW) of every output frame; None: the plan's shape
-        :param mode: 1 = bilinear, anything else = the nearest-lower tap
-        :param out: ``"host"``: a numpy array (in a pinned block of the library's pool when it fits, as ``LinearAlign.transform``
-                    returns it); ``"device"``: a torch tensor on the plan's device
-        :return: (S, OH, OW) float32, or (S, OH, OW, 3) uint8
-        """
+    def _warp_args(self, images, matrices, offsets, fills, out_shape, out):
+        """The arguments ``transform_batch`` and ``stack_batch`` share, checked and marshalled: ``(ptrs, n, is_dev, keep, maps, fills,
+        oh, ow)`` with `maps` the (n, 6) float32 table of the C ABI and `fills` a contiguous float32 (n,) array."""
         if out not in ("host", "device"):
             raise ValueError("out must be 'host' or 'device', not %r" % (out,))
         ptrs, n, is_dev, keep = self._warp_frames(images)
@@ -302,21 +289,43 @@ class BatchPlan(SiftPlan):
         oh, ow = (int(v) for v in (self.shape if out_shape is None else out_shape))
         if oh < 0 or ow < 0:
             raise ValueError("negative output shape")
+        return ptrs, n, is_dev, keep, maps, f, oh, ow
+
+    def _host_result(self, oshape, odtype):
+        """a numpy array for a result: in a pinned block of the library's pool when it fits, an ordinary one otherwise"""
+        count = int(numpy.prod(oshape))
+        if self.pinned_results and count:
+            try:
+                return _lib.pinned_empty(count, odtype).reshape(oshape)
+            except MemoryError:                 # beyond the pool's limit (_lib.pinned_pool): an ordinary array
+                pass
+        return numpy.empty(oshape, odtype)
+
+    def transform_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, out="host"):
+        """Affine warp of S frames of the plan's shape in one launch (``siftmi_batch_transform``): frame s of the result is bit
+        for bit ``LinearAlign.transform(matrices[s], offsets[s], images[s], fills[s], mode)``.  One synchronisation, one upload of a
+        host stack (separate host arrays: one each) and one copy back of a host result.  A map with a non-finite entry gives ``fills[s]`` wherever it reaches
+        (all NaN: the whole plane).  Device memory: the result, plus the frames when they come from the host.
+
+        :param images: S frames, all numpy arrays or all device tensors, or one (S, H, W[, 3]) stack: float32 H x W, or uint8
+                       H x W x 3 for an RGB plan (nothing is converted)
+        :param matrices: (S, 2, 2) or (S, 4), acting on (y, x) as in ``LinearAlign.transform``
+        :param offsets: (S, 2)
+        :param fills: a scalar or (S,); for an RGB plan every value must lie in [0, 255]
+        :param out_shape: (OH, OW) of every output frame; None: the plan's shape
+        :param mode: 1 = bilinear, anything else = the nearest-lower tap
+        :param out: ``"host"``: a numpy array (in a pinned block of the library's pool when it fits, as ``LinearAlign.transform``
+                    returns it); ``"device"``: a torch tensor on the plan's device
+        :return: (S, OH, OW) float32, or (S, OH, OW, 3) uint8
+        """
+        ptrs, n, is_dev, keep, maps, f, oh, ow = self._warp_args(images, matrices, offsets, fills, out_shape, out)
         oshape, odtype = ((n, oh, ow, 3), numpy.uint8) if self.RGB else ((n, oh, ow), numpy.float32)
         if out == "device":
             import torch
             result = torch.empty(oshape, dtype=torch.uint8 if self.RGB else torch.float32, device=torch.device("cuda", self.device))
             optr = result.data_ptr()
         else:
-            result = None
-            count = int(numpy.prod(oshape))
-            if self.pinned_results and count:
-                try:
-                    result = _lib.pinned_empty(count, odtype).reshape(oshape)
-                except MemoryError:                 # beyond the pool's limit (_lib.pinned_pool): an ordinary array
-                    result = None
-            if result is None:
-                result = numpy.empty(oshape, odtype)
+            result = self._host_result(oshape, odtype)
             optr = result.ctypes.data
         ms = C.c_double(0)
         with self._sem:
@@ -325,6 +334,59 @@ class BatchPlan(SiftPlan):
         self.last_transform_ms = ms.value
         del keep
         return result
+
+    #: the reducers of ``stack_batch`` and their codes in include/siftmi.h
+    STACK_REDUCERS = {"sum": 0, "mean": 1, "median": 2}
+    #: frames a median may take (SIFTMI_STACK_MEDIAN_MAX)
+    STACK_MEDIAN_MAX = 64
+
+    def stack_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, reduce="mean", empty=numpy.nan, coverage=False,
+                    out="host"):
+        """Warp S float32 frames as ``transform_batch`` does and reduce them to ONE plane in the same launch
+        (``siftmi_batch_stack``): the S warped planes are never written, only the result crosses the
+        link.  Per output pixel a frame is *live* where its warped value is not its fill for a geometric reason -- the source point
+        lies in the frame, left of and above the cut at W - 0.5, H - 0.5; a map with a non-finite entry leaves its frame out wherever
+        the entry reaches, an all-NaN map everywhere.  The result is, over the live frames of the pixel,
+
+        * ``"sum"``: the float32 sum in the order of the frames,
+        * ``"mean"``: that sum divided by their number,
+        * ``"median"``: the median in the total order of float32 -- the middle value, or half the sum of the two middle ones
+          (``numpy.median`` of the live values wherever they are finite); at most 64 frames,
+
+        and `empty` where no frame is live.  Greyscale plans only.
+
+        :param images, matrices, offsets, fills, out_shape, mode: as for ``transform_batch``
+        :param reduce: ``"sum"``, ``"mean"`` or ``"median"``
+        :param empty: the value of a pixel that no frame covers
+        :param coverage: also return the number of live frames of every pixel
+        :param out: ``"host"``: numpy arrays; ``"device"``: torch tensors on the plan's device
+        :return: the (OH, OW) float32 plane, or ``(plane, coverage)`` with the (OH, OW) int32 counts
+        """
+        if self.RGB:
+            raise RuntimeError("stack_batch reduces float32 frames; an RGB plan has no stack reduction")
+        if reduce not in self.STACK_REDUCERS:
+            raise ValueError("reduce must be one of %s, not %r" % (sorted(self.STACK_REDUCERS), reduce))
+        ptrs, n, is_dev, keep, maps, f, oh, ow = self._warp_args(images, matrices, offsets, fills, out_shape, out)
+        if reduce == "median" and n > self.STACK_MEDIAN_MAX:
+            raise ValueError("a median takes at most %d frames, not %d" % (self.STACK_MEDIAN_MAX, n))
+        if out == "device":
+            import torch
+            dev = torch.device("cuda", self.device)
+            plane = torch.empty((oh, ow), dtype=torch.float32, device=dev)
+            cover = torch.empty((oh, ow), dtype=torch.int32, device=dev) if coverage else None
+            pptr, cptr = plane.data_ptr(), (cover.data_ptr() if coverage else None)
+        else:
+            plane = self._host_result((oh, ow), numpy.float32)
+            cover = self._host_result((oh, ow), numpy.int32) if coverage else None
+            pptr, cptr = plane.ctypes.data, (cover.ctypes.data if coverage else None)
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_batch_stack(self._handle, ptrs, n, is_dev, pptr, cptr, int(out == "device"), ow, oh,
+                                                     maps.ctypes.data, f.ctypes.data, int(mode), self.STACK_REDUCERS[reduce],
+                                                     C.c_float(empty), C.byref(ms)))
+        self.last_stack_ms = ms.value
+        del keep
+        return (plane, cover) if coverage else plane
 
     def minmax(self):
         raise RuntimeError("BatchPlan keeps no per-frame min/max; use SiftPlan")

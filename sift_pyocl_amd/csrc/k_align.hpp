@@ -56,6 +56,47 @@ __global__ __launch_bounds__(256) void transform_kernel(const float *__restrict_
     out[(size_t)y * OW + x] = transform_pixel(image, a, W, H, x, y);
 }
 
+// transform_pixel in two steps, for a kernel that samples several frames per thread (k_stack.hpp): the source point with its taps
+// -- every load of the pixel -- and then the value.  Such a kernel takes the taps of a few frames before it forms their values, so
+// that their gathers are in flight together; transform_pixel itself is one frame's loads and arithmetic in one block, and
+// writing it as the two steps changes the code the warp kernels compile to, so it stays as it is.  The steps repeat its text
+// operation for operation (the same products, sums and comparisons, the same taps replaced by `fill`, bilinear_mix itself):
+// transform_value(transform_taps(...)) is transform_pixel(...) bit for bit, which tests/test_gpu_stack.py holds the kernels to.
+struct WarpTaps { float tx, ty, p, px, py, pn; bool inside; };
+
+__device__ __forceinline__ WarpTaps transform_taps(const float *__restrict__ image, const AffineArgs &a, int W, int H, int x, int y) {
+    float tx = a.m2 * (float)y + a.m3 * (float)x;
+    float ty = a.m0 * (float)y + a.m1 * (float)x;
+    tx += a.off1; ty += a.off0;
+    WarpTaps t{tx, ty, a.fill, a.fill, a.fill, a.fill, 0.0f <= tx && tx < (float)W && 0.0f <= ty && ty < (float)H};
+    if (t.inside) {
+        const int tx_prev = (int)tx, ty_prev = (int)ty;
+        const float *r0 = image + (size_t)ty_prev * W + tx_prev;
+        t.p = r0[0];
+        if (a.mode == 1) {
+            const bool xin = tx_prev + 1 < W, yin = ty_prev + 1 < H;
+            t.px = xin ? r0[1] : a.fill;
+            t.py = yin ? r0[W] : a.fill;
+            t.pn = (xin && yin) ? r0[W + 1] : a.fill;
+        }
+    }
+    return t;
+}
+
+__device__ __forceinline__ float transform_value(const WarpTaps &t, const AffineArgs &a, int W, int H) {
+    float interp = a.fill;
+    if (t.inside) interp = a.mode == 1 ? bilinear_mix(t.tx, t.ty, (int)t.tx, (int)t.ty, t.p, t.px, t.py, t.pn) : t.p;
+    if (t.tx >= (float)W + -0.5f) interp = a.fill;
+    if (t.ty >= (float)H + -0.5f) interp = a.fill;
+    return interp;
+}
+
+// Where the warp's value is not `fill` for a geometric reason: the source point lies in the image and left of / above the cut
+// at W - 0.5, H - 0.5 (a subset of `inside`; false for a non-finite tx or ty).  What a stack reduction counts as coverage.
+__device__ __forceinline__ bool transform_live(const WarpTaps &t, int W, int H) {
+    return 0.0f <= t.tx && t.tx < (float)W + -0.5f && 0.0f <= t.ty && t.ty < (float)H + -0.5f;
+}
+
 // RGB8: one thread produces 4 consecutive output pixels = 12 bytes, stored as three dwords when the row segment is
 // 4-byte aligned (byte stores with stride 3 were store-issue bound: 0.13 ms at 4096^2 against 0.04 ms for f32).
 __device__ __forceinline__ void transform_rgb_pixel(const uint8_t *__restrict__ image, const AffineArgs &a, int W, int H,

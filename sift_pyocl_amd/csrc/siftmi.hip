@@ -23,6 +23,7 @@
 #include "k_descriptor.hpp"
 #include "k_align.hpp"
 #include "k_align_batch.hpp"
+#include "k_stack.hpp"
 #include "k_pyramid.hpp"
 #include "k_tail.hpp"
 #include "siftmath.hpp"
@@ -2002,6 +2003,97 @@ int grow_device(void **ptr, size_t *cap, size_t need) {
 }
 }  // namespace
 
+namespace {
+// What siftmi_batch_transform and siftmi_batch_stack share around their launch.
+struct WarpIo {
+    hipStream_t stream = nullptr;
+    int W = 0, H = 0;
+    void *dst = nullptr;                           // where the kernel writes: the caller's device output, or the batch's staging
+};
+
+// Before the launch: the ordering after the NULL stream for device pointers, the batch-owned buffers (staging of host frames
+// and of a host result of `out_bytes`, the table of `n_images` frames as a pinned block and its device copy), the upload of
+// host frames -- one copy per run of frames that lie back to back in host memory (a stack is ONE copy) -- and of the table.
+int warp_begin(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, size_t px, void *out,
+               int32_t out_is_device, size_t out_bytes, const float *maps, const float *fills, int32_t mode, WarpIo *io) {
+    HIPCHK(hipSetDevice(b->device));
+    siftmi_plan *p0 = b->lanes[0];
+    hipStream_t stream = p0->stream;               // every lane is idle between two calls on the handle
+    const int W = p0->W, H = p0->H;
+    const size_t in_bytes = (size_t)W * H * px;
+    // a device pointer on either side: ordered after what the NULL stream was given for it (siftmi.h, conventions)
+    if ((images_are_device && n_images > 0) || out_is_device) HIPCHK(hipDeviceSynchronize());
+    int rc;
+    if (!images_are_device && (rc = grow_device(&b->warp_in, &b->warp_in_bytes, in_bytes * (size_t)n_images))) return rc;
+    if (!out_is_device && (rc = grow_device(&b->warp_out, &b->warp_out_bytes, out_bytes))) return rc;
+    const size_t tab_bytes = sizeof(WarpFrame) * (size_t)n_images;
+    if ((rc = grow_device(&b->warp_tab, &b->warp_tab_bytes, tab_bytes))) return rc;
+    if (b->warp_tab_host_bytes < tab_bytes) {
+        if (b->warp_tab_host) hipHostFree(b->warp_tab_host);
+        b->warp_tab_host = nullptr; b->warp_tab_host_bytes = 0;
+        size_t cap = 4096;
+        while (cap < tab_bytes) cap *= 2;
+        hipError_t e = hipHostMalloc(&b->warp_tab_host, cap, hipHostMallocDefault);
+        if (e != hipSuccess) { b->warp_tab_host = nullptr; return fail(SIFTMI_ENOMEM, "hipHostMalloc(%zu): %s", cap, hipGetErrorString(e)); }
+        b->warp_tab_host_bytes = cap;
+    }
+    if (!b->ev_wa) { HIPCHK(hipEventCreate(&b->ev_wa)); HIPCHK(hipEventCreate(&b->ev_wb)); }
+    if (!images_are_device) {
+        for (int32_t i = 0; i < n_images;) {
+            int32_t j = i + 1;
+            while (j < n_images && (const uint8_t *)images[j] == (const uint8_t *)images[j - 1] + in_bytes) j++;
+            hipError_t e = hipMemcpyAsync((uint8_t *)b->warp_in + (size_t)i * in_bytes, images[i], in_bytes * (size_t)(j - i), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(SIFTMI_EDEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e)); }
+            i = j;
+        }
+    }
+    if (n_images > 0) {
+        WarpFrame *tab = static_cast<WarpFrame *>(b->warp_tab_host);
+        for (int32_t i = 0; i < n_images; i++) {
+            const float *m = maps + 6 * (size_t)i;
+            tab[i].image = images_are_device ? images[i] : (const void *)((const uint8_t *)b->warp_in + (size_t)i * in_bytes);
+            tab[i].a = AffineArgs{m[0], m[1], m[2], m[3], m[4], m[5], fills[i], mode};
+        }
+        HIPCHK(hipMemcpyAsync(b->warp_tab, tab, tab_bytes, hipMemcpyHostToDevice, stream));
+    }
+    io->stream = stream; io->W = W; io->H = H;
+    io->dst = out_is_device ? out : b->warp_out;
+    return SIFTMI_OK;
+}
+
+// After the launch (bracketed by ev_wa / ev_wb): a host result copied back from the staging -- `bytes0` to `host0`, then the
+// `bytes1` behind them to `host1` when there is a second piece --, the one synchronisation, and kernel_ms from the event pair.
+int warp_end(siftmi_batch *b, const WarpIo &io, void *host0, size_t bytes0, void *host1, size_t bytes1, double *kernel_ms) {
+    if (host0 && bytes0) {
+        hipError_t e = hipMemcpyAsync(host0, io.dst, bytes0, hipMemcpyDeviceToHost, io.stream);
+        if (e == hipSuccess && host1 && bytes1) e = hipMemcpyAsync(host1, (const uint8_t *)io.dst + bytes0, bytes1, hipMemcpyDeviceToHost, io.stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(io.stream); return fail(SIFTMI_EDEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e)); }
+    }
+    HIPCHK(hipStreamSynchronize(io.stream));       // (the pinned table and the caller's frames are free again from here on)
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, b->ev_wa, b->ev_wb);
+        *kernel_ms = ms;
+    }
+    return SIFTMI_OK;
+}
+
+// The one launch site of the stack reduction (k_stack.hpp): S frames of W x H from the device table to one OH x OW plane and,
+// unless null, its coverage.  S == 0 (sum or mean) fills the plane with `empty` and the coverage with 0.
+void launch_stack(hipStream_t st, int reduce, const WarpFrame *frames, int S, float *out, int32_t *coverage, int W, int H, int OW, int OH,
+                  float empty) {
+    const dim3 grid((unsigned)((OW + 63) / 64), (unsigned)((OH + 3) / 4)), block(64, 4);
+    if (reduce == SIFTMI_STACK_MEDIAN)
+        hipLaunchKernelGGL(stack_median_kernel, grid, block, (size_t)stack_median_slots(S) * 256 * sizeof(uint32_t), st, frames, S, out, coverage, W, H,
+                           OW, OH, empty);
+    else if (reduce == SIFTMI_STACK_MEAN)
+        hipLaunchKernelGGL(stack_reduce_kernel<true>, grid, block, 0, st, frames, S, out, coverage, W, H, OW, OH, empty);
+    else
+        hipLaunchKernelGGL(stack_reduce_kernel<false>, grid, block, 0, st, frames, S, out, coverage, W, H, OW, OH, empty);
+}
+}  // namespace
+
 // The warp of siftmi_plan_transform for n frames in one launch (k_align_batch.hpp).
 int siftmi_batch_transform(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device,
                            int32_t channels, void *out, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps,
@@ -2018,67 +2110,54 @@ int siftmi_batch_transform(siftmi_batch *b, const void *const *images, int32_t n
     for (int32_t i = 0; i < n_images; i++) if (!images[i]) return fail(SIFTMI_EINVAL, "null image %d", i);
     if (kernel_ms) *kernel_ms = 0;
     if (empty || b->lanes.empty()) return SIFTMI_OK;
-    HIPCHK(hipSetDevice(b->device));
-    siftmi_plan *p0 = b->lanes[0];
-    hipStream_t stream = p0->stream;               // every lane is idle between two calls on the handle
-    const int W = p0->W, H = p0->H;
     const size_t px = channels == 1 ? 4 : 3;
-    const size_t in_bytes = (size_t)W * H * px, frame_out = (size_t)OW * OH * px, out_bytes = frame_out * (size_t)n_images;
-    // a device pointer on either side: ordered after what the NULL stream was given for it (siftmi.h, conventions)
-    if (images_are_device || out_is_device) HIPCHK(hipDeviceSynchronize());
-    int rc;
-    if (!images_are_device && (rc = grow_device(&b->warp_in, &b->warp_in_bytes, in_bytes * (size_t)n_images))) return rc;
-    if (!out_is_device && (rc = grow_device(&b->warp_out, &b->warp_out_bytes, out_bytes))) return rc;
-    const size_t tab_bytes = sizeof(WarpFrame) * (size_t)n_images;
-    if ((rc = grow_device(&b->warp_tab, &b->warp_tab_bytes, tab_bytes))) return rc;
-    if (b->warp_tab_host_bytes < tab_bytes) {
-        if (b->warp_tab_host) hipHostFree(b->warp_tab_host);
-        b->warp_tab_host = nullptr; b->warp_tab_host_bytes = 0;
-        size_t cap = 4096;
-        while (cap < tab_bytes) cap *= 2;
-        hipError_t e = hipHostMalloc(&b->warp_tab_host, cap, hipHostMallocDefault);
-        if (e != hipSuccess) { b->warp_tab_host = nullptr; return fail(SIFTMI_ENOMEM, "hipHostMalloc(%zu): %s", cap, hipGetErrorString(e)); }
-        b->warp_tab_host_bytes = cap;
-    }
-    if (!b->ev_wa) { HIPCHK(hipEventCreate(&b->ev_wa)); HIPCHK(hipEventCreate(&b->ev_wb)); }
-    // host frames: one copy per run of frames that lie back to back in host memory (a stack is ONE copy)
-    if (!images_are_device) {
-        for (int32_t i = 0; i < n_images;) {
-            int32_t j = i + 1;
-            while (j < n_images && (const uint8_t *)images[j] == (const uint8_t *)images[j - 1] + in_bytes) j++;
-            hipError_t e = hipMemcpyAsync((uint8_t *)b->warp_in + (size_t)i * in_bytes, images[i], in_bytes * (size_t)(j - i), hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(SIFTMI_EDEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e)); }
-            i = j;
-        }
-    }
-    WarpFrame *tab = static_cast<WarpFrame *>(b->warp_tab_host);
-    for (int32_t i = 0; i < n_images; i++) {
-        const float *m = maps + 6 * (size_t)i;
-        tab[i].image = images_are_device ? images[i] : (const void *)((const uint8_t *)b->warp_in + (size_t)i * in_bytes);
-        tab[i].a = AffineArgs{m[0], m[1], m[2], m[3], m[4], m[5], fills[i], mode};
-    }
-    HIPCHK(hipMemcpyAsync(b->warp_tab, tab, tab_bytes, hipMemcpyHostToDevice, stream));
-    void *dst = out_is_device ? out : b->warp_out;
+    const size_t out_bytes = (size_t)OW * OH * px * (size_t)n_images;
+    WarpIo io;
+    int rc = warp_begin(b, images, n_images, images_are_device, px, out, out_is_device, out_bytes, maps, fills, mode, &io);
+    if (rc) return rc;
     const int xcols = channels == 1 ? 64 : 256;   // RGB: 4 pixels per thread
     const dim3 grid((unsigned)((OW + xcols - 1) / xcols), (unsigned)((OH + 3) / 4), (unsigned)n_images), block(64, 4);
-    hipEventRecord(b->ev_wa, stream);
+    hipEventRecord(b->ev_wa, io.stream);
     if (channels == 1)
-        hipLaunchKernelGGL(transform_batch_kernel, grid, block, 0, stream, (const WarpFrame *)b->warp_tab, (float *)dst, W, H, OW, OH);
+        hipLaunchKernelGGL(transform_batch_kernel, grid, block, 0, io.stream, (const WarpFrame *)b->warp_tab, (float *)io.dst, io.W, io.H, OW, OH);
     else
-        hipLaunchKernelGGL(transform_rgb_batch_kernel, grid, block, 0, stream, (const WarpFrame *)b->warp_tab, (uint8_t *)dst, W, H, OW, OH);
-    hipEventRecord(b->ev_wb, stream);
-    if (!out_is_device) {
-        hipError_t e = hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(SIFTMI_EDEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e)); }
-    }
-    HIPCHK(hipStreamSynchronize(stream));          // (the pinned table and the caller's frames are free again from here on)
-    HIPCHK(hipGetLastError());
-    if (kernel_ms) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, b->ev_wa, b->ev_wb);
-        *kernel_ms = ms;
-    }
-    return SIFTMI_OK;
+        hipLaunchKernelGGL(transform_rgb_batch_kernel, grid, block, 0, io.stream, (const WarpFrame *)b->warp_tab, (uint8_t *)io.dst, io.W, io.H, OW, OH);
+    hipEventRecord(b->ev_wb, io.stream);
+    return warp_end(b, io, out_is_device ? nullptr : out, out_bytes, nullptr, 0, kernel_ms);
+}
+
+// S frames warped and reduced to one plane in one launch (k_stack.hpp).  Without a frame the reduction kernel itself is the fill
+// path: launched with S == 0 it writes `empty` and coverage 0 to every pixel.
+int siftmi_batch_stack(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, float *out,
+                       int32_t *coverage, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps, const float *fills,
+                       int32_t mode, int32_t reduce, float empty, double *kernel_ms) {
+    if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (n_images < 0) return fail(SIFTMI_EINVAL, "negative image count");
+    if (n_images > 65535) return fail(SIFTMI_EINVAL, "%d frames: more than 65535", n_images);
+    if (reduce != SIFTMI_STACK_SUM && reduce != SIFTMI_STACK_MEAN && reduce != SIFTMI_STACK_MEDIAN)
+        return fail(SIFTMI_EINVAL, "reduce must be 0 (sum), 1 (mean) or 2 (median), got %d", reduce);
+    if (reduce == SIFTMI_STACK_MEDIAN && n_images > SIFTMI_STACK_MEDIAN_MAX)
+        return fail(SIFTMI_EINVAL, "median of %d frames: more than %d", n_images, SIFTMI_STACK_MEDIAN_MAX);
+    if (OW < 0 || OH < 0) return fail(SIFTMI_EINVAL, "negative output shape");
+    if (OH > 4 * 65535) return fail(SIFTMI_EINVAL, "output height %d: more than %d rows (4 per grid row)", OH, 4 * 65535);
+    if (!b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8) return fail(SIFTMI_EINVAL, "a batch created for RGB8 frames has no stack reduction");
+    const bool nothing = OW == 0 || OH == 0;
+    if (n_images > 0 && (!images || !maps || !fills)) return fail(SIFTMI_EINVAL, "null argument");
+    if (!nothing && !out) return fail(SIFTMI_EINVAL, "null output");
+    for (int32_t i = 0; i < n_images; i++) if (!images[i]) return fail(SIFTMI_EINVAL, "null image %d", i);
+    if (kernel_ms) *kernel_ms = 0;
+    if (nothing || b->lanes.empty()) return SIFTMI_OK;
+    static_assert(SIFTMI_STACK_MEDIAN_MAX == SIFT_STACK_MEDIAN_MAX, "siftmi.h and k_stack.hpp disagree on the median's cap");
+    const size_t plane = (size_t)OW * OH * sizeof(float);
+    WarpIo io;
+    int rc = warp_begin(b, images, n_images, images_are_device, sizeof(float), out, out_is_device, plane * (coverage ? 2 : 1), maps, fills, mode, &io);
+    if (rc) return rc;
+    // a host result: the plane, then the coverage, in the batch's staging
+    int32_t *cov = out_is_device ? coverage : (coverage ? reinterpret_cast<int32_t *>((uint8_t *)io.dst + plane) : nullptr);
+    hipEventRecord(b->ev_wa, io.stream);
+    launch_stack(io.stream, n_images ? reduce : SIFTMI_STACK_SUM, (const WarpFrame *)b->warp_tab, n_images, (float *)io.dst, cov, io.W, io.H, OW, OH, empty);
+    hipEventRecord(b->ev_wb, io.stream);
+    return warp_end(b, io, out_is_device ? nullptr : out, plane, coverage, plane, kernel_ms);
 }
 
 int siftmi_plan_records_device(const siftmi_plan *p, const siftmi_keypoint **records, int64_t *count) {
