@@ -674,8 +674,10 @@ int siftmi_stage_gradient_maps(int32_t device_id, const float *planes, int32_t n
                                int32_t oct_lo, int32_t oct_hi, int32_t blocks, float *gmap, float *omap);
 int siftmi_stage_shrink(int32_t device_id, const float *in, float *out, int32_t W, int32_t H);
 int siftmi_stage_convert(int32_t device_id, const void *in, int32_t in_dtype, float *out, int32_t W, int32_t H);
-/* device versions of the "siftmath v1" functions, elementwise over n floats (test hook) */
-int siftmi_stage_math(int32_t device_id, int32_t fn /*0 exp,1 exp2,2 sin,3 cos,4 atan2*/, const float *a,
+/* device versions of the "siftmath v1" functions, elementwise over n floats (test hook).  fn: 0 exp, 1 exp2, 2 sin, 3 cos,
+ * 4 atan2(a, b); 5 / 6 the fast paths expf_fast(a) / atan2f_fast(a, b); 7 div_by_reciprocal(a, b); 8 the candidate that
+ * expf_fast_try returns, usable or not, and 9 its `ok` as 1.0f / 0.0f; 10 / 11 the same of atan2f_fast_try(a, b). */
+int siftmi_stage_math(int32_t device_id, int32_t fn, const float *a,
                       const float *b, float *out, int64_t n);
 
 #ifdef __cplusplus

@@ -29,7 +29,8 @@
 static inline double om_from_bits(uint64_t u) { double d; memcpy(&d, &u, 8); return d; }
 static inline uint64_t om_to_bits(double d) { uint64_t u; memcpy(&u, &d, 8); return u; }
 
-/* round-to-nearest-even integer of |z| < 2^51 using only IEEE additions */
+/* round-to-nearest-even integer of |z| < 2^51 using only IEEE additions.  (From 2^51 on the sum is no longer exact and
+ * this is not rint(); every caller below bounds its argument first: |z| <= 151 in exp / exp2, |z| < 2^30 in sin/cos.) */
 static inline double om_rint(double z) {
     volatile double t = z + 0x1.8p52; /* volatile: forbid algebraic simplification */
     return t - 0x1.8p52;
@@ -58,16 +59,21 @@ static inline double om_exp_core(double r) {
 /* 2^k as a double for -1022 <= k <= 1023 */
 static inline double om_pow2i(int k) { return om_from_bits((uint64_t)(k + 1023) << 52); }
 
-static inline float om_expf(float xf) {
-    if (xf != xf) return xf;
-    if (xf > 89.0f) return __builtin_inff();
-    if (xf < -104.0f) return 0.0f;
+/* the binary64 value that om_expf rounds, for -104 <= xf <= 89 */
+static inline double om_expf_f64(float xf) {
     double x = (double)xf;
     double kd = om_rint(x * 0x1.71547652b82fep+0);     /* x*log2(e) */
     double r = (x - kd * 0x1.62e42fee00000p-1)          /* ln2 hi (32 bits): product exact */
                   - kd * 0x1.a39ef35793c76p-33;         /* ln2 lo */
     double v = om_exp_core(r) * om_pow2i((int)kd);
-    return (float)v;
+    return v;
+}
+
+static inline float om_expf(float xf) {
+    if (xf != xf) return xf;
+    if (xf > 89.0f) return __builtin_inff();
+    if (xf < -104.0f) return 0.0f;
+    return (float)om_expf_f64(xf);
 }
 
 /* 2^y, used for InitSigma * pow(2, (s+ds)/3)  (image.cl:354) */
@@ -84,9 +90,10 @@ static inline float om_exp2f(float yf) {
 
 /* sin and cos of a float, binary64 evaluation.  Accurate for |x| < ~1e5 (angles here
  * are in [-pi, pi]); beyond that the quadrant reduction loses accuracy but stays
- * deterministic.  NaN/Inf in -> NaN out. */
+ * deterministic.  Domain: |x| <= 2^30, where the quadrant number still fits an int
+ * (|x 2/pi| < 2^30); every other argument -- larger, Inf, NaN -- gives NaN for both. */
 static inline void om_sincosf(float xf, float *sn, float *cs) {
-    if (xf != xf || xf - xf != 0.0f) { *sn = xf - xf; *cs = xf - xf; return; }
+    if (!(__builtin_fabsf(xf) <= 0x1p30f)) { *sn = __builtin_nanf(""); *cs = __builtin_nanf(""); return; }
     double x = (double)xf;
     double kd = om_rint(x * 0x1.45f306dc9c883p-1);      /* x * 2/pi */
     double r = (x - kd * 0x1.921fb54400000p+0)          /* pi/2 hi (33 bits) */
@@ -122,10 +129,8 @@ static inline void om_sincosf(float xf, float *sn, float *cs) {
     *cs = (float)co;
 }
 
-/* atan2(y, x) with C99 special-case semantics for zeros; NaN in -> NaN out.
- * Infinities are not expected on this path and are treated as NaN. */
-static inline float om_atan2f(float yf, float xf) {
-    if (yf != yf || xf != xf || yf - yf != 0.0f || xf - xf != 0.0f) return (yf - yf) + (xf - xf);
+/* the binary64 value (signed) that om_atan2f rounds, for finite yf, xf */
+static inline double om_atan2f_f64(float yf, float xf) {
     double ay = (double)__builtin_fabsf(yf), ax = (double)__builtin_fabsf(xf);
     double res;
     if (ay == 0.0 && ax == 0.0) {
@@ -165,7 +170,14 @@ static inline float om_atan2f(float yf, float xf) {
     }
     if (__builtin_signbitf(xf)) res = 0x1.921fb54442d18p+1 - res;  /* pi - res */
     if (__builtin_signbitf(yf)) res = -res;
-    return (float)res;
+    return res;
+}
+
+/* atan2(y, x) with C99 special-case semantics for zeros; NaN in -> NaN out.
+ * Infinities are not expected on this path and are treated as NaN. */
+static inline float om_atan2f(float yf, float xf) {
+    if (yf != yf || xf != xf || yf - yf != 0.0f || xf - xf != 0.0f) return (yf - yf) + (xf - xf);
+    return (float)om_atan2f_f64(yf, xf);
 }
 
 #endif

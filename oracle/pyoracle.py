@@ -76,6 +76,46 @@ def atan2f_array(y, x):
     return out
 
 
+def exp2f_array(x):
+    x = np.ascontiguousarray(x, np.float32); out = np.empty_like(x)
+    lib().so_exp2f_array(_p(x), _p(out), C.c_int64(x.size))
+    return out
+
+
+def sincosf_array(x):
+    """(sin, cos) of every element"""
+    x = np.ascontiguousarray(x, np.float32); sn = np.empty_like(x); cs = np.empty_like(x)
+    lib().so_sincosf_array(_p(x), _p(sn), _p(cs), C.c_int64(x.size))
+    return sn, cs
+
+
+def expf_f64_array(x):
+    """the binary64 value that expf rounds to binary32 (for -104 <= x <= 89; elsewhere the special result, widened)"""
+    x = np.ascontiguousarray(x, np.float32); out = np.empty(x.shape, np.float64)
+    lib().so_expf_f64_array(_p(x), _p(out), C.c_int64(x.size))
+    return out
+
+
+def atan2f_f64_array(y, x):
+    """the signed binary64 value that atan2f rounds to binary32 (finite operands; elsewhere the NaN result, widened)"""
+    y = np.ascontiguousarray(y, np.float32); x = np.ascontiguousarray(x, np.float32); out = np.empty(x.shape, np.float64)
+    lib().so_atan2f_f64_array(_p(y), _p(x), _p(out), C.c_int64(x.size))
+    return out
+
+
+def boundary_distance(v):
+    """Distance of binary64 values from the nearest binary32 round-to-nearest boundary, on the bits: of the 29 bits that
+    the conversion discards, |low - 2^28| (2^28 is the half-way pattern).  In binary64 ulps of v; meaningful for v in the
+    binary32 normal range."""
+    low = (np.ascontiguousarray(v, np.float64).view(np.uint64) & np.uint64(0x1fffffff)).astype(np.int64)
+    return np.abs(low - 0x10000000)
+
+
+def boundary_side(v):
+    """True where the discarded bits of v lie above the half-way pattern (the conversion rounds the magnitude up)"""
+    return (np.ascontiguousarray(v, np.float64).view(np.uint64) & np.uint64(0x1fffffff)) > np.uint64(0x10000000)
+
+
 def gaussian_taps(sigma, size):
     out = np.empty(size, np.float32)
     lib().so_gaussian_taps(C.c_float(np.float32(sigma)), C.c_int(size), _p(out))

@@ -50,7 +50,7 @@ float so_expf(float x) { return om_expf(x); }
 float so_exp2f(float x) { return om_exp2f(x); }
 float so_atan2f(float y, float x) { return om_atan2f(y, x); }
 void so_sincosf(float x, float *s, float *c) { om_sincosf(x, s, c); }
-/* array forms (the device fast paths are checked on 10^7 arguments) */
+/* array forms (the device functions are checked on millions of arguments, tests/test_gpu_parity.py, tests/test_gpu_math_hard.py) */
 void so_expf_array(const float *x, float *out, int64_t n) {
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; i++) out[i] = om_expf(x[i]);
@@ -58,6 +58,26 @@ void so_expf_array(const float *x, float *out, int64_t n) {
 void so_atan2f_array(const float *y, const float *x, float *out, int64_t n) {
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; i++) out[i] = om_atan2f(y[i], x[i]);
+}
+void so_exp2f_array(const float *x, float *out, int64_t n) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) out[i] = om_exp2f(x[i]);
+}
+void so_sincosf_array(const float *x, float *sn, float *cs, int64_t n) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) om_sincosf(x[i], sn + i, cs + i);
+}
+/* the binary64 value that om_expf / om_atan2f round to binary32 (where the float function returns a special value
+ * without evaluating -- NaN, beyond the range tests, a non-finite operand -- that value, widened) */
+void so_expf_f64_array(const float *x, double *out, int64_t n) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++)
+        out[i] = (x[i] >= -104.0f && x[i] <= 89.0f) ? om_expf_f64(x[i]) : (double)om_expf(x[i]);
+}
+void so_atan2f_f64_array(const float *y, const float *x, double *out, int64_t n) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++)
+        out[i] = (y[i] - y[i] == 0.0f && x[i] - x[i] == 0.0f) ? om_atan2f_f64(y[i], x[i]) : (double)om_atan2f(y[i], x[i]);
 }
 
 /* ------------------------------------------------------------------ A3: Gaussian taps

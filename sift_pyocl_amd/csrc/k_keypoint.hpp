@@ -808,7 +808,8 @@ __global__ __launch_bounds__(256) void gradient_maps_kernel(OctaveTable tab, int
     }
 }
 
-// elementwise siftmath (test hook); fn 5 / 6: the Ziv fast paths of exp / atan2
+// elementwise siftmath (test hook); fn 5 / 6: the Ziv fast paths of exp / atan2; fn 8 / 9 and 10 / 11: what their *_try forms
+// return -- the candidate as it is, usable or not, and `ok` as 1.0f / 0.0f
 __global__ void math_kernel(int fn, const float *__restrict__ a, const float *__restrict__ bb, float *__restrict__ out, int64_t n) {
     __shared__ double fold[36];
     siftmath::load_atan_fold(fold);
@@ -816,6 +817,7 @@ __global__ void math_kernel(int fn, const float *__restrict__ a, const float *__
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         float s, c;
+        bool ok;
         switch (fn) {
             case 0: out[i] = siftmath::expf_(a[i]); break;
             case 1: out[i] = siftmath::exp2f_(a[i]); break;
@@ -824,6 +826,10 @@ __global__ void math_kernel(int fn, const float *__restrict__ a, const float *__
             case 5: out[i] = siftmath::expf_fast(a[i]); break;
             case 6: out[i] = siftmath::atan2f_fast(a[i], bb[i], fold); break;
             case 7: out[i] = siftmath::div_by_reciprocal(a[i], bb[i], 1.0f / bb[i]); break;
+            case 8: out[i] = siftmath::expf_fast_try(a[i], ok); break;
+            case 9: siftmath::expf_fast_try(a[i], ok); out[i] = ok ? 1.0f : 0.0f; break;
+            case 10: out[i] = siftmath::atan2f_fast_try(a[i], bb[i], fold, ok); break;
+            case 11: siftmath::atan2f_fast_try(a[i], bb[i], fold, ok); out[i] = ok ? 1.0f : 0.0f; break;
             default: out[i] = siftmath::atan2f_(a[i], bb[i]); break;
         }
     }

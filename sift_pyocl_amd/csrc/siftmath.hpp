@@ -10,7 +10,7 @@
 //
 // Specification (identical constants and operation order are restated independently by the test
 // oracle): exp: x = k ln2 + r, Taylor degree 14 in r; exp2: r = (y-k) ln2; sin/cos: Cody-Waite
-// pi/2 reduction (33-bit hi part), Taylor to r^19 / r^20; atan2: octant table atan(k/8), k from an
+// pi/2 reduction (33-bit hi part), Taylor to r^19 / r^20, defined for |x| <= 2^30 and NaN beyond; atan2: octant table atan(k/8), k from an
 // exactly rounded f32 quotient, t = (num - c den)/(den + c num), Taylor to t^17.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,9 +31,11 @@ SM_HD double from_bits(uint64_t u) {
 #endif
 }
 
-// round to nearest-even integer for |z| < 2^51, additions only
+// round to nearest-even integer
 SM_HD double rint_magic(double z) {
-    // v_rndne_f64 on the device / roundsd on the host: round-half-even, == (z + 1.5*2^52) - 1.5*2^52
+    // v_rndne_f64 on the device / roundsd on the host: round-half-even.  For |z| < 2^51 this is (z + 1.5*2^52) - 1.5*2^52,
+    // the additions-only form the oracle uses; from 2^51 on that sum is no longer exact and the two differ, so every
+    // caller bounds its argument first: |z| <= 151 in exp / exp2, |z| < 2^30 in sin/cos.
     return __builtin_rint(z);
 }
 
@@ -80,8 +82,10 @@ SM_HD float exp2f_(float yf) {
     return (float)v;
 }
 
+// Domain: |x| <= 2^30, where the quadrant number still fits an int (|x 2/pi| < 2^30); every other argument -- larger, Inf,
+// NaN -- gives NaN for both.
 SM_HD void sincosf_(float xf, float *sn, float *cs) {
-    if (xf != xf || xf - xf != 0.0f) { *sn = xf - xf; *cs = xf - xf; return; }
+    if (!(__builtin_fabsf(xf) <= 0x1p30f)) { *sn = __builtin_nanf(""); *cs = __builtin_nanf(""); return; }
     double x = (double)xf;
     double kd = rint_magic(x * 0x1.45f306dc9c883p-1);
     double r = (x - kd * 0x1.921fb54400000p+0) - kd * 0x1.0b4611a626331p-34;
@@ -164,8 +168,14 @@ SM_HD float atan2f_(float yf, float xf) {
 // (error <= 2^-45 relative, see the notes at each) and return its rounding only when the binary64 value is farther
 // than 2^-39 from every rounding boundary -- then both evaluations sit on the same side of the boundary and round to
 // the same binary32 number.  Otherwise (probability 2^-15 per call), and outside the guarded argument range, the
-// defining function is evaluated.  Results are therefore bit-identical to expf_ / atan2f_ for every argument
-// (checked on 10^7 arguments per function against the CPU oracle, tests/test_gpu_parity.py).
+// defining function is evaluated.  Results are therefore bit-identical to expf_ / atan2f_ for every argument.
+// Checked against the CPU oracle (i) on 10^7 random arguments per function (tests/test_gpu_parity.py), which almost never
+// come near the rule, and (ii) on the arguments that do (tests/golden/math_hard.npz, tests/test_gpu_math_hard.py): ~20 000
+// exp arguments -- among them every float of [-12, 0] and of the ends of the reduction interval (|r| > 0.33) whose binary64
+// value lies within 64 units of 2^-52 of a boundary -- and ~32 000 atan2 operand pairs, by distance d of the defining
+// function's binary64 value from the boundary: the candidate is refused for d <= 8192 - 512, accepted and already equal to
+// the defining function's float for d >= 8192 + 512 (512: twice the 2^-45), never accepted outside the guarded range, and
+// wherever it is accepted it is the defining function's float.  Seven of the refused candidates do round the other way.
 #if defined(__HIPCC__)
 
 // T[swap + 2 * (x < 0)][k]: the octant fold applied to atan(k / 8), correctly rounded:

@@ -30,8 +30,50 @@ def _params(**kw):
 
 
 # ----------------------------------------------------------------------------- siftmath
+def _around(v, ulps):
+    """the float32 v and the `ulps` floats on either side of it"""
+    return (np.array([v], np.float32).view(np.int32) + np.arange(-ulps, ulps + 1, dtype=np.int32)).view(np.float32)
+
+
+def _log_uniform(rng, n, lo_exp, hi_exp):
+    """both signs, uniform exponent in [lo_exp, hi_exp), uniform mantissa"""
+    return (np.ldexp(1.0 + rng.random(n), rng.integers(lo_exp, hi_exp, n)) * rng.choice([-1.0, 1.0], n)).astype(np.float32)
+
+
+def _unary_sweep(fn, rng, n=1 << 22):
+    """2^22 arguments of exp (0), exp2 (1), sin / cos (2, 3) over the whole argument type: any bit pattern; both sides and the
+    exact values of every range test of the four functions (-104, 89, -150, 128, and 2^30 of sin / cos); results in the binary32
+    sub-normal range; +-0, the smallest sub-normals, +-inf, NaN; for sin / cos also 2^k pi/2 +- a few ulps up to k = 29,
+    multiples of pi/2, uniform exponents up to 2^30 and, separately, from 2^30 to FLT_MAX (NaN for both)."""
+    parts = [rng.integers(0, 2 ** 32, n // 2, dtype=np.uint64).astype(np.uint32).view(np.float32)]
+    for edge in (-104.0, 89.0, -150.0, 128.0, 104.0, -89.0, 150.0, -128.0, 2.0 ** 30, -2.0 ** 30):
+        parts.append(_around(edge, 512))
+    tiny = np.array([0, 1, 2, 3, 0x007fffff, 0x00800000, 0x00800001], np.uint32)
+    parts.append(np.concatenate([tiny, tiny | np.uint32(0x80000000)]).view(np.float32))
+    parts.append(np.array([np.inf, -np.inf, np.nan, -np.nan, 3.4028235e38, -3.4028235e38], np.float32))
+    m = n // 16
+    if fn == 0:
+        parts += [rng.uniform(-104.0, -87.3, 2 * m), rng.uniform(88.0, 89.0, m), rng.uniform(-110.0, 95.0, 2 * m), _log_uniform(rng, m, -149, 7)]
+    elif fn == 1:
+        parts += [rng.uniform(-150.0, -126.0, 2 * m), rng.uniform(127.0, 128.0, m), rng.uniform(-155.0, 133.0, 2 * m), _log_uniform(rng, m, -149, 8),
+                  np.arange(-152, 131, dtype=np.float32), np.arange(-152, 131, dtype=np.float32) + np.float32(0.5)]      # exact powers, ties of rint
+    else:
+        half_pi = np.float32(np.pi / 2)
+        parts += [np.concatenate([_around(np.float32(np.ldexp(np.pi / 2, k)), 8) for k in range(-2, 30)])]
+        parts[-1] = np.concatenate([parts[-1], -parts[-1]])
+        q = rng.integers(-(1 << 29), 1 << 29, m)                                          # multiples of pi/2, |x| < 2^30
+        parts += [(q * (np.pi / 2)).astype(np.float32), (rng.integers(-4096, 4096, m) * half_pi).astype(np.float32),
+                  _log_uniform(rng, 3 * m, -30, 30), _log_uniform(rng, m, 30, 128), _log_uniform(rng, m // 2, -149, -100)]
+    a = np.concatenate([np.asarray(p, np.float32) for p in parts])
+    lo, hi = (-110.0, 95.0) if fn == 0 else (-155.0, 133.0) if fn == 1 else (-8.0, 8.0)
+    assert a.size <= n
+    return np.concatenate([a, rng.uniform(lo, hi, n - a.size).astype(np.float32)])
+
+
 @pytest.mark.parametrize("fn", [0, 1, 2, 3, 4])
 def test_device_math_bit_exact(siftlib, oracle, fn):
+    """The defining functions on the device against the oracle's (array entry points): 200 000 arguments of the working ranges
+    and, for the unary ones, 2^22 more over the whole argument type (_unary_sweep).  NaN results are compared as "is NaN"."""
     rng = np.random.default_rng(fn)
     n = 200000
     if fn == 0:
@@ -45,25 +87,30 @@ def test_device_math_bit_exact(siftlib, oracle, fn):
     b = (rng.standard_normal(n) * 10.0 ** rng.integers(-3, 3, n)).astype(np.float32)
     if fn == 4:
         a[:6] = [0, -0.0, 0, 1, -1, 0]; b[:6] = [0, 0, -0.0, 0, 0, -1]
+    else:
+        a = np.concatenate([a, _unary_sweep(fn, np.random.default_rng(1000 + fn))]); b = a
+        n = a.size
     out = np.empty(n, np.float32)
     assert siftlib.siftmi_stage_math(0, fn, _p(a), _p(b), _p(out), n) == 0
-    L = oracle.lib()
-    exp = np.empty(n, np.float32)
-    s, c = C.c_float(), C.c_float()
-    for i in range(n):
-        if fn == 0: exp[i] = L.so_expf(C.c_float(a[i]))
-        elif fn == 1: exp[i] = L.so_exp2f(C.c_float(a[i]))
-        elif fn in (2, 3):
-            L.so_sincosf(C.c_float(a[i]), C.byref(s), C.byref(c)); exp[i] = s.value if fn == 2 else c.value
-        else: exp[i] = L.so_atan2f(C.c_float(a[i]), C.c_float(b[i]))
-    assert np.array_equal(out.view(np.uint32), exp.view(np.uint32))
+    if fn == 0: exp = oracle.expf_array(a)
+    elif fn == 1: exp = oracle.exp2f_array(a)
+    elif fn in (2, 3): exp = oracle.sincosf_array(a)[fn - 2]
+    else: exp = oracle.atan2f_array(a, b)
+    if fn in (2, 3):                                                                    # sin / cos are total: NaN beyond 2^30
+        beyond = ~(np.abs(a) <= np.float32(2.0 ** 30))
+        assert beyond.sum() > 1 << 20 and np.isnan(out[beyond]).all() and np.isfinite(out[~beyond]).all()
+    if fn in (0, 1):                                                                    # the sweep reaches sub-normal results
+        assert ((exp > 0) & (exp < np.float32(2.0 ** -126))).sum() > 1 << 17
+    bad = np.nonzero((out.view(np.uint32) != exp.view(np.uint32)) & ~(np.isnan(out) & np.isnan(exp)))[0]
+    assert bad.size == 0, (fn, bad.size, a[bad[:4]], b[bad[:4]], out[bad[:4]], exp[bad[:4]])
 
 
 @pytest.mark.parametrize("fn", [5, 6])
 def test_device_fast_paths_equal_the_defining_functions(siftlib, oracle, fn):
     """siftmath's Ziv fast paths (expf_fast, atan2f_fast: fused binary64 evaluation + rounding-safety test, fallback to
     the defining function) against the oracle's expf / atan2f on 10^7 arguments each: pipeline-like ranges, wide
-    ranges, exact ties of the octant selection, zeros / infinities / NaN / sub-normal results."""
+    ranges, exact ties of the octant selection, zeros / infinities / NaN / sub-normal results.  (Random arguments hardly
+    ever come near a rounding boundary: tests/test_gpu_math_hard.py holds the ones that do.)"""
     rng = np.random.default_rng(100 + fn)
     n = 1 << 20
     for rnd in range(10):
