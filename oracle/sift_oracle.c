@@ -675,13 +675,20 @@ int64_t so_match(const so_record *k1, int64_t n1, const so_record *k2, int64_t n
  *   - a list-2 keypoint that fails `inside && mask != 0` is NOT skipped: its distance is 0 (the accumulation
  *     is what the mask guards), so it competes as a perfect match;
  *   - (c, r) = (int)x, (int)y.
+ * The position rule, stated for both modes: a coordinate v is convertible iff fabsf(v) < 2147483648.0f (false for NaN and
+ * +-inf); then (int)v truncates toward zero, so every v in (-1, 1) gives 0, -0.0 included (the reference's literal cast).
+ * A coordinate that is not convertible is never cast -- that cast is undefined in C (gcc on x86 happens to give INT_MIN, a
+ * saturating device INT_MAX / INT_MIN / 0 for NaN) -- and its keypoint is outside: no index is formed.  inside iff both
+ * coordinates are convertible and 0 <= r < rh && 0 <= c < rw; on = inside && valid[(size_t)r * rw + c] != 0, any non-zero
+ * int8 counting, negative values included.
  * roi_mode 2 ("strict", an extension): keypoints of either list that are not inside the array on a non-zero
  * mask pixel do not take part at all.  roi_mode 0: no mask (== so_match).
  * mutual != 0 (extension): a pair (i, j) is kept only if i is also the nearest list-1 keypoint of j, over the
  * same masked distances, ties to the smallest index (the reference's strict '<' scan order). */
-static inline int so_roi_inside(const so_record *k, int rw, int rh) {
-    const int c = (int)k->x, r = (int)k->y;
-    return r < rh && c < rw && r >= 0 && c >= 0;
+static inline int so_roi_inside(const so_record *k, int rw, int rh, int *c, int *r) {
+    if (!(fabsf(k->x) < 2147483648.0f && fabsf(k->y) < 2147483648.0f)) return 0;
+    *c = (int)k->x; *r = (int)k->y;
+    return *r < rh && *c < rw && *r >= 0 && *c >= 0;
 }
 static inline int so_l1(const uint8_t *a, const uint8_t *b) {
     int dist = 0;
@@ -698,13 +705,15 @@ int64_t so_match_ex(const so_record *k1, int64_t n1, const so_record *k2, int64_
     int32_t *rev = (int32_t *)malloc((size_t)(n2 > 0 ? n2 : 1) * sizeof(int32_t));
     if (!best || !f1 || !f2 || !rev) { free(best); free(f1); free(f2); free(rev); return -1; }
     for (int64_t i = 0; roi_mode && i < n1; i++) {
-        const int in = so_roi_inside(&k1[i], rw, rh);
-        const int on = in && valid[(size_t)((int)k1[i].y) * rw + (int)k1[i].x] != 0;
+        int c = 0, r = 0;
+        const int in = so_roi_inside(&k1[i], rw, rh, &c, &r);
+        const int on = in && valid[(size_t)r * rw + c] != 0;
         f1[i] = roi_mode == 1 ? (in && !on) : !on;
     }
     for (int64_t j = 0; roi_mode && j < n2; j++) {
-        const int in = so_roi_inside(&k2[j], rw, rh);
-        const int on = in && valid[(size_t)((int)k2[j].y) * rw + (int)k2[j].x] != 0;
+        int c = 0, r = 0;
+        const int in = so_roi_inside(&k2[j], rw, rh, &c, &r);
+        const int on = in && valid[(size_t)r * rw + c] != 0;
         f2[j] = on ? 0 : (roi_mode == 1 ? 1 : 2);
     }
 #pragma omp parallel for schedule(dynamic, 64)

@@ -155,8 +155,12 @@ __global__ __launch_bounds__(256) void match_merge_kernel(const MatchPartial *__
     }
 }
 
-// ROI flags of one keypoint list (matching_cpu.cl:155-158,171-174): (c, r) = (int)x, (int)y;
-// inside = 0 <= r < roi_height && 0 <= c < roi_width;  on = inside && valid[r*roi_width + c] != 0.
+// ROI flags of one keypoint list (matching_cpu.cl:155-158,171-174).  The contract, for a coordinate v (float32):
+//   v is convertible iff fabsf(v) < 2147483648.0f (false for NaN and +-inf); then (int)v truncates toward zero, the reference's
+//   literal cast: every v in (-1, 1) gives 0, -0.0 included.  A coordinate that is not convertible is never converted (the cast
+//   is undefined in C++ and saturates / turns NaN into 0 on this device): the keypoint is outside and no index is formed.
+//   (c, r) = (int)x, (int)y;  inside = both convertible && 0 <= r < roi_height && 0 <= c < roi_width;
+//   on = inside && valid[(size_t)r*roi_width + c] != 0 -- any non-zero int8 counts, negative values included.
 //   as_query: bit 0 = 0, bit 1 = dropped       (mode 1: inside && !on;  mode 2: !on)
 //   as_list : 0 / 1 (distance forced to 0, mode 1 && !on) / 2 (excluded, mode 2 && !on)
 __global__ void match_roi_flags_kernel(const uint8_t *__restrict__ kp, int n, const int8_t *__restrict__ valid,
@@ -164,7 +168,9 @@ __global__ void match_roi_flags_kernel(const uint8_t *__restrict__ kp, int n, co
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *k = reinterpret_cast<const float *>(kp + (size_t)i * 144);
-    const int c = (int)k[0], r = (int)k[1];
+    const float x = k[0], y = k[1];
+    const bool convertible = fabsf(x) < 2147483648.0f && fabsf(y) < 2147483648.0f;
+    const int c = convertible ? (int)x : -1, r = convertible ? (int)y : -1;
     const bool inside = r < rh && c < rw && r >= 0 && c >= 0;
     const bool on = inside && valid[(size_t)r * rw + c] != 0;
     as_query[i] = (mode == 1 ? (inside && !on) : !on) ? 2 : 0;

@@ -105,7 +105,13 @@ class MatchPlan(object):
         :param raw_results: if true return the 2D array of indexes of matching keypoints (not the actual keypoints)
         :param roi_mode: 0 (default) ignores the region of interest, exactly like the reference, whose ``match`` never
                          reaches its ``matching_valid`` kernel; "reference" / 1 runs that kernel's semantics literally
-                         (matching_cpu.cl:136-199); "strict" / 2 drops every keypoint that is not on a non-zero pixel
+                         (matching_cpu.cl:136-199); "strict" / 2 drops every keypoint that is not on a non-zero pixel.
+                         A keypoint's pixel is ``(c, r) = (int)x, (int)y``, truncated toward zero (every coordinate in (-1, 1)
+                         gives 0); it is inside the mask iff ``0 <= r < rows and 0 <= c < columns``, and on it iff the mask is
+                         non-zero there (any non-zero int8, negative values included).  A coordinate ``v`` that is NaN, infinite
+                         or has ``abs(v) >= 2**31`` is never converted: its keypoint is outside.  Mode 1 drops a first-list
+                         keypoint that is inside and not on the mask and gives a second-list keypoint that is not on it the
+                         distance 0; mode 2 leaves every keypoint that is not on the mask out
         :param mutual: keep only pairs that are nearest neighbours in both directions (extension)
         :param window: (extension) None, or the half width of a search window in pixels, a scalar or an ``(wx, wy)`` pair (x first,
                        like the record fields; ``inf`` is allowed).  Keypoint j of the second list is then a *candidate* of keypoint
@@ -730,11 +736,14 @@ class MatchPlan(object):
 
     def set_roi(self, roi):
         """Defines the region of interest (match.py:312-320): 2D array, non zero where pixels are valid.  As in the
-        reference it has no effect on ``match()`` unless ``roi_mode`` is given."""
+        reference it has no effect on ``match()`` unless ``roi_mode`` is given.  The mask is converted as
+        ``numpy.ascontiguousarray(roi, numpy.int8)`` converts it (the reference's line): a uint8 200 becomes -56 and stays
+        valid, an int16 256 and a float 0.5 become 0.  A mask that is not 2D is refused and the mask in force stays."""
         with self._sem:
-            self.roi = numpy.ascontiguousarray(roi, numpy.int8)
-            if self.roi.ndim != 2:
+            roi = numpy.ascontiguousarray(roi, numpy.int8)
+            if roi.ndim != 2:
                 raise RuntimeError("the region of interest must be a 2D array")
+            self.roi = roi
             _lib.check(_lib.lib().siftmi_match_set_roi(self._handle, self.roi.ctypes.data, self.roi.shape[1], self.roi.shape[0]))
 
     def unset_roi(self):

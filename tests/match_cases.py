@@ -457,21 +457,7 @@ def flag_cases(n1, seed=7):
 
 def flags_restated(case):
     """(a', b', rows of a', rows of b') without flags: what the masked call means for lists whose queries all carry ONE descriptor.
-    An excluded element or a dropped query is deleted; an element at forced distance 0 gets the queries' descriptor."""
-    a, b, mode = case.a, case.b, case.roi_mode
-    H, W = case.roi.shape
-
-    def on(k):
-        c, r = k["x"].astype(np.int64), k["y"].astype(np.int64)
-        inside = (r >= 0) & (r < H) & (c >= 0) & (c < W)
-        return inside, inside & (case.roi[np.clip(r, 0, H - 1), np.clip(c, 0, W - 1)] != 0)
-
-    in1, on1 = on(a); _, on2 = on(b)
-    keep1 = ~(in1 & ~on1) if mode == 1 else on1
-    b2 = b.copy()
-    if mode == 1:
-        b2["desc"][~on2] = a["desc"][0]
-        keep2 = np.ones(len(b), bool)
-    else:
-        keep2 = on2
-    return a[keep1], b2[keep2], np.nonzero(keep1)[0], np.nonzero(keep2)[0]
+    An excluded element or a dropped query is deleted; an element at forced distance 0 gets the queries' descriptor.  Which
+    keypoint gets which flag is stated once, in tests/roi_ref.py."""
+    import roi_ref
+    return roi_ref.restated(case.a, case.b, case.roi, case.roi_mode)
