@@ -13,9 +13,17 @@
  * message retrievable from siftmi_last_error() (thread-local).  Handles are opaque, bound to one
  * HIP device and one HIP stream, and must be used by one host thread at a time (the Python
  * wrapper holds the reference's per-plan semaphore, plan.py:156,439 / match.py:117,215).
- * "is_device" pointers are HIP device pointers on the plan's device; the call orders itself
- * after work already submitted to the NULL stream by synchronising the device once on entry
- * when a device pointer is passed.
+ * "is_device" pointers are HIP device pointers on the plan's device, inputs and outputs alike
+ * (out_is_device, pairs_is_device, mask_is_device ...).  What is guaranteed for them, and tested
+ * entry point by entry point and pointer by pointer (tests/test_gpu_ordering.py):
+ *   - a device pointer is read and written only after everything the caller had enqueued, on ANY
+ *     stream of the process (blocking or not, the NULL stream included), before the call: the call
+ *     synchronises the device once on entry when a device pointer is passed -- the library's own
+ *     streams are non-blocking, so nothing else orders them after a caller's stream.  No event or
+ *     synchronisation is needed between producing the data and the call, and none between
+ *     enqueueing a write to an output buffer and the call that overwrites it;
+ *   - host and device results are complete when the call returns: they may be read at once, on
+ *     the host or on any stream.
  */
 #ifndef SIFTMI_H
 #define SIFTMI_H
@@ -246,7 +254,7 @@ int siftmi_batch_fetch(siftmi_batch *batch, siftmi_keypoint *out, int32_t out_is
  *   maps         n x 6 floats: matrix[4] then offset[2] of each frame, as siftmi_plan_transform takes them
  *   fills        n floats; RGB8: each in [0, 255], as for siftmi_plan_transform
  *   kernel_ms    optional, hipEvent duration of the launch (0 when nothing is launched)
- * Device pointers are ordered after the NULL stream as everywhere (conventions, above).  n_images == 0 or an empty output
+ * Device pointers are ordered after the caller's streams as everywhere (conventions, above).  n_images == 0 or an empty output
  * launches nothing and returns 0.  SIFTMI_EINVAL, nothing launched: a null handle, a null table or output with work to do, a
  * null frame, channels other than 1 or 3, a negative shape or count, n_images > 65535, out_height > 262140. */
 int siftmi_batch_transform(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
@@ -277,7 +285,7 @@ int siftmi_batch_minmax(const siftmi_batch *batch, float *mins, float *maxs, int
  *   out          OH x OW float32, host (staged in a buffer the batch owns and grows, with the coverage behind it) or device
  *   coverage     OH x OW int32 where `out` lives, or NULL
  *   kernel_ms    optional, hipEvent duration of the launch (0 when nothing is launched)
- * One launch, one synchronisation; device pointers are ordered after the NULL stream as everywhere.  An empty output launches
+ * One launch, one synchronisation; device pointers are ordered after the caller's streams as everywhere.  An empty output launches
  * nothing and returns 0.  n_images == 0 with a non-empty output fills `out` with `empty` and `coverage` with 0: the reduction
  * kernel launched over no frame is the fill.  SIFTMI_EINVAL, nothing launched: a null handle, a null table or output with work
  * to do, a null frame, a batch created for RGB8, an unknown `reduce`, SIFTMI_STACK_MEDIAN with n_images > 64, a negative shape

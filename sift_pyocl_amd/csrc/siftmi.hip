@@ -1554,6 +1554,12 @@ int siftmi_plan_keypoints(siftmi_plan *p, const void *image, int32_t image_dtype
     p->host_cap = pinned ? (int)(capacity < 0x7fffffff ? capacity : 0x7fffffff) : 0;
     int64_t n = 0;
     int32_t ovf = 0;
+    // a device result array: ordered after what the caller's streams were given for it (siftmi.h, conventions); a device frame
+    // is synchronised for by plan_enqueue
+    if (out_is_device == SIFTMI_OUT_DEVICE && out && capacity > 0 && !image_is_device) {
+        HIPCHK(hipSetDevice(p->device));
+        HIPCHK(hipDeviceSynchronize());
+    }
     int rc = plan_run(p, image, image_dtype, image_is_device, true, &n, &ovf);
     p->host_out = nullptr; p->host_cap = 0;
     if (rc) {
@@ -1585,6 +1591,7 @@ int siftmi_plan_fetch(siftmi_plan *p, siftmi_keypoint *out, int32_t out_is_devic
     if (first < 0 || count < 0 || first + count > p->last_count) return fail(SIFTMI_EINVAL, "record range out of bounds");
     if (count == 0) return SIFTMI_OK;
     HIPCHK(hipSetDevice(p->device));
+    if (out_is_device) HIPCHK(hipDeviceSynchronize());   // a device destination: ordered after the caller's streams (siftmi.h, conventions)
     HIPCHK(hipMemcpyAsync(out, p->records + first, (size_t)count * sizeof(KpRecord),
                           out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
@@ -1974,8 +1981,13 @@ int siftmi_batch_fetch(siftmi_batch *b, siftmi_keypoint *out, int32_t out_is_dev
     if (first < 0 || count < 0 || (size_t)(first + count) * sizeof(KpRecord) > b->arena_used) return fail(SIFTMI_EINVAL, "record range out of bounds");
     if (count == 0) return SIFTMI_OK;
     HIPCHK(hipSetDevice(b->device));
+    // a device destination: ordered after the caller's streams (siftmi.h, conventions) -- the copy below runs on the NULL stream,
+    // which does not wait for the non-blocking streams a caller such as PyTorch works on
+    if (out_is_device) HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, b->arena + (size_t)first * sizeof(KpRecord), (size_t)count * sizeof(KpRecord),
                      out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    // a device-to-device hipMemcpy need not wait on the host; the result is complete on return for readers on any stream
+    if (out_is_device) HIPCHK(hipStreamSynchronize(nullptr));
     return SIFTMI_OK;
 }
 
@@ -2011,7 +2023,7 @@ struct WarpIo {
     void *dst = nullptr;                           // where the kernel writes: the caller's device output, or the batch's staging
 };
 
-// Before the launch: the ordering after the NULL stream for device pointers, the batch-owned buffers (staging of host frames
+// Before the launch: the ordering after the caller's streams for device pointers, the batch-owned buffers (staging of host frames
 // and of a host result of `out_bytes`, the table of `n_images` frames as a pinned block and its device copy), the upload of
 // host frames -- one copy per run of frames that lie back to back in host memory (a stack is ONE copy) -- and of the table.
 int warp_begin(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, size_t px, void *out,
@@ -2021,7 +2033,7 @@ int warp_begin(siftmi_batch *b, const void *const *images, int32_t n_images, int
     hipStream_t stream = p0->stream;               // every lane is idle between two calls on the handle
     const int W = p0->W, H = p0->H;
     const size_t in_bytes = (size_t)W * H * px;
-    // a device pointer on either side: ordered after what the NULL stream was given for it (siftmi.h, conventions)
+    // a device pointer on either side: ordered after what the caller's streams were given for it (siftmi.h, conventions)
     if ((images_are_device && n_images > 0) || out_is_device) HIPCHK(hipDeviceSynchronize());
     int rc;
     if (!images_are_device && (rc = grow_device(&b->warp_in, &b->warp_in_bytes, in_bytes * (size_t)n_images))) return rc;
@@ -2178,7 +2190,7 @@ int siftmi_plan_transform(siftmi_plan *p, const void *image, int32_t image_is_de
     const size_t px = channels == 1 ? 4 : 3;
     const size_t in_bytes = (size_t)p->W * p->H * px, out_bytes = (size_t)OW * OH * px;
     const void *src = image;
-    // a device pointer on either side: ordered after what the NULL stream was given for it (siftmi.h, conventions)
+    // a device pointer on either side: ordered after what the caller's streams were given for it (siftmi.h, conventions)
     if ((image && image_is_device) || out_is_device) HIPCHK(hipDeviceSynchronize());
     if (!image) {
         const int want = channels == 1 ? SIFTMI_F32 : SIFTMI_RGB8;
