@@ -236,6 +236,11 @@ int siftmi_batch_keypoints(siftmi_batch *batch, const void *const *images, int32
 int siftmi_batch_keypoints_into(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t image_dtype,
                                 int32_t images_are_device, siftmi_keypoint *const *host_outs, const int64_t *host_caps,
                                 int64_t *counts, int64_t *offsets, int64_t *total_parked, int32_t *overflow);
+/* siftmi_batch_fetch: records [first, first + count) of what the last siftmi_batch_keypoints[_into] parked, 0 <= first,
+ * 0 <= count, first + count <= *total_parked (checked without forming the sum); anything else is SIFTMI_EINVAL and writes
+ * nothing.  count == 0 copies nothing and needs no `out`.  A call of siftmi_batch_keypoints[_into] that FAILED leaves nothing
+ * to fetch (every range but a count of 0 is refused until the next call succeeds), as it leaves no min / max; a call
+ * refused for its arguments before it started (a null table, a wrong dtype code, ...) leaves the previous batch as it was. */
 int siftmi_batch_fetch(siftmi_batch *batch, siftmi_keypoint *out, int32_t out_is_device, int64_t first, int64_t count);
 /* The two ends of aligning a stack (the reference aligns frame by frame: LinearAlign.align, alignment.py:225-360).
  * siftmi_batch_minmax     min and max of every frame of the last FINISHED siftmi_batch_keypoints[_into], in input order: each

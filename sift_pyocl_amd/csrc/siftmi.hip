@@ -1588,7 +1588,8 @@ int siftmi_plan_keypoints(siftmi_plan *p, const void *image, int32_t image_dtype
 
 int siftmi_plan_fetch(siftmi_plan *p, siftmi_keypoint *out, int32_t out_is_device, int64_t first, int64_t count) {
     if (!p || (count > 0 && !out)) return fail(SIFTMI_EINVAL, "null argument");
-    if (first < 0 || count < 0 || first + count > p->last_count) return fail(SIFTMI_EINVAL, "record range out of bounds");
+    // (no sum of the two: first + count can overflow)
+    if (first < 0 || count < 0 || first > p->last_count || count > p->last_count - first) return fail(SIFTMI_EINVAL, "record range out of bounds");
     if (count == 0) return SIFTMI_OK;
     HIPCHK(hipSetDevice(p->device));
     if (out_is_device) HIPCHK(hipDeviceSynchronize());   // a device destination: ordered after the caller's streams (siftmi.h, conventions)
@@ -1955,15 +1956,16 @@ int siftmi_batch_keypoints_into(siftmi_batch *b, const void *const *images, int3
     if (htime) fprintf(stderr, "[siftmi] batch of %d: waiting for lanes %.0f us, enqueueing %.0f us\n", n_images, t_retire, t_enqueue);
     for (int i = n_images > (int)L ? n_images - (int)L : 0; i < n_images && !rc; i++) rc = batch_retire(b, (size_t)i % L, overflow);
     b->host_outs = nullptr; b->host_caps = nullptr; b->cur_images = nullptr;
+    if (!rc) BATCHCHK(hipDeviceSynchronize());                 // the parking copies
     if (rc) {                                // nothing of this call may still read the caller's frames or write its arrays
         std::string keep = g_err;
         if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
         batch_drain(b);
+        b->arena_used = 0;                   // a failed call leaves nothing to fetch (and no min / max: mm_frames is -1)
         g_err = keep;
         return rc;
     }
 #undef BATCHCHK
-    HIPCHK(hipDeviceSynchronize());                            // the parking copies
     for (int i = 0; i < n_images; i++) { counts[i] = b->counts[(size_t)i]; offsets[i] = b->offsets[(size_t)i]; }
     *total_parked = (int64_t)(b->arena_used / sizeof(KpRecord));
     b->mm_frames = n_images;
@@ -1978,7 +1980,9 @@ int siftmi_batch_keypoints(siftmi_batch *b, const void *const *images, int32_t n
 
 int siftmi_batch_fetch(siftmi_batch *b, siftmi_keypoint *out, int32_t out_is_device, int64_t first, int64_t count) {
     if (!b || (count > 0 && !out)) return fail(SIFTMI_EINVAL, "null argument");
-    if (first < 0 || count < 0 || (size_t)(first + count) * sizeof(KpRecord) > b->arena_used) return fail(SIFTMI_EINVAL, "record range out of bounds");
+    // in records, and without a sum of the two: first + count can overflow, and so can its product with the record size
+    const int64_t total = (int64_t)(b->arena_used / sizeof(KpRecord));
+    if (first < 0 || count < 0 || first > total || count > total - first) return fail(SIFTMI_EINVAL, "record range out of bounds");
     if (count == 0) return SIFTMI_OK;
     HIPCHK(hipSetDevice(b->device));
     // a device destination: ordered after the caller's streams (siftmi.h, conventions) -- the copy below runs on the NULL stream,

@@ -20,7 +20,7 @@ import warnings
 import numpy as np
 import pytest
 
-from util import assert_same_keypoints, smooth_noise, sort_kp
+from util import assert_same_keypoints, lattice, smooth_noise, sort_kp
 from test_gpu_params import CASES as PAR_CASES
 
 BORDER = 5                      # par.BorderDist
@@ -28,21 +28,6 @@ LATTICE_ROWS = 256              # ext_rows of the lattice runs: 62 x 256 sample 
 SIFT_EXT_BUF = 128
 TILED = (333, 402)
 MARCH = (1280, 1536)            # march_plane(): the marching blur, refinement in its own launch
-
-
-def lattice(shape, period=7, sigma=2.0, seed=11, jitter=1):
-    """Alternating-sign Gaussian blobs on a jittered square grid: about one DoG extremum per 36 samples."""
-    import scipy.ndimage as ndi
-    rng = np.random.default_rng(seed)
-    H, W = shape
-    ys, xs = np.arange(period // 2, H, period), np.arange(period // 2, W, period)
-    yy, xx = np.meshgrid(ys, xs, indexing="ij")
-    sign = np.where((np.arange(len(ys))[:, None] + np.arange(len(xs))[None, :]) % 2 == 0, 1.0, -1.0)
-    yy = np.clip(yy + rng.integers(-jitter, jitter + 1, yy.shape), 0, H - 1)
-    xx = np.clip(xx + rng.integers(-jitter, jitter + 1, xx.shape), 0, W - 1)
-    img = np.zeros(shape, np.float64)
-    img[yy, xx] = sign * (0.6 + 0.4 * rng.random(yy.shape))
-    return ndi.gaussian_filter(img, sigma).astype(np.float32)
 
 
 def extrema_strip_rows(W, H, border=BORDER, min_strips=2000):

@@ -14,6 +14,21 @@ def smooth_noise(shape, seed=3, sigma=3.0):
     return ndi.gaussian_filter(np.random.default_rng(seed).random(shape), sigma).astype(np.float32)
 
 
+def lattice(shape, period=7, sigma=2.0, seed=11, jitter=1):
+    """Alternating-sign Gaussian blobs on a jittered square grid: about one DoG extremum per 36 samples."""
+    import scipy.ndimage as ndi
+    rng = np.random.default_rng(seed)
+    H, W = shape
+    ys, xs = np.arange(period // 2, H, period), np.arange(period // 2, W, period)
+    yy, xx = np.meshgrid(ys, xs, indexing="ij")
+    sign = np.where((np.arange(len(ys))[:, None] + np.arange(len(xs))[None, :]) % 2 == 0, 1.0, -1.0)
+    yy = np.clip(yy + rng.integers(-jitter, jitter + 1, yy.shape), 0, H - 1)
+    xx = np.clip(xx + rng.integers(-jitter, jitter + 1, xx.shape), 0, W - 1)
+    img = np.zeros(shape, np.float64)
+    img[yy, xx] = sign * (0.6 + 0.4 * rng.random(yy.shape))
+    return ndi.gaussian_filter(img, sigma).astype(np.float32)
+
+
 def multiscale_noise(shape, seed=5):
     import scipy.ndimage as ndi
     rng = np.random.default_rng(seed)
