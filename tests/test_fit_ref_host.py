@@ -74,7 +74,7 @@ def test_degenerate_and_empty():
     assert np.isfinite(r[fr.MEANS]).all() and np.isfinite(r[fr.MOMENTS]).all()
     same = np.tile(np.float32([7.5, 9.25, 1.0, 2.0]), (40, 1))
     r = fr.fit_pts(same)
-    assert r[fr.STATUS] == fr.DEGENERATE and (r[fr.MOMENTS] == 0).all()          # scale = 0: fmax(1.0, scale) decides
+    assert r[fr.STATUS] == fr.DEGENERATE and (r[fr.MOMENTS] == 0).all()          # det = scale = 0: DEGENERATE with or without fmax (fit_cases.tiny_cluster: fmax decides)
     kp1, kp2, pairs, truth = fr.make_case(300, 11)
     pts = fr.gather(kp1, kp2, pairs)
     for n in (1, 2):

@@ -157,7 +157,7 @@ def test_degenerate_positions(siftlib, mp):
     same["x"] = 7.5; same["y"] = 9.25
     pairs = np.stack([idx[:40], idx[:40]], axis=1)
     want = fr.fit(same, same, pairs)
-    assert want[fr.STATUS] == fr.DEGENERATE and (want[fr.MOMENTS] == 0).all()    # scale = 0: fmax(1.0, scale) decides
+    assert want[fr.STATUS] == fr.DEGENERATE and (want[fr.MOMENTS] == 0).all()    # det = scale = 0: no reading of the rule accepts it (fit_cases.tiny_cluster is where fmax decides)
     assert_bits(abi_fit(siftlib, mp, same, same, pairs)[0], want, "identical")
 
 
