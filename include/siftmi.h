@@ -303,6 +303,44 @@ int siftmi_batch_stack(siftmi_batch *batch, const void *const *images, int32_t n
                        float *out /* OH x OW */, int32_t *coverage /* OH x OW, may be null */, int32_t out_is_device,
                        int32_t out_width, int32_t out_height, const float *maps /* n x 6 */, const float *fills /* n */,
                        int32_t mode, int32_t reduce, float empty, double *kernel_ms);
+/* The mean of the samples that survive an outlier rejection (extension; DESIGN.md section 7 row 18, restated in numpy by
+ * tests/stack_clip_ref.py):
+ * siftmi_batch_stack_clip  warps n <= 64 float32 frames as siftmi_batch_stack does and reduces them per output pixel to a weighted
+ *                         mean over a kept set K of the live frames, in one launch (stack_clip_kernel, csrc/k_stack_clip.hpp).
+ *                         v_s, live_s, c and key() are siftmi_batch_stack's; osum is its ordered sum over K in ascending s (the
+ *                         first value starts the accumulator); binary32, one rounding per operation.  K starts as the live frames.
+ *                           TRIM    order the live samples by (key(v_s), s) ascending; h = min(n_high, c - 1),
+ *                                   l = min(n_low, c - 1 - h); the last h and the first l leave K.  At least one sample stays, the
+ *                                   high side is served first, a positive NaN sorts above +inf and goes with the high side
+ *                           SIGMA   kl2 = kappa_low * kappa_low, kh2 = kappa_high * kappa_high; at most `iters` passes, each:
+ *                                   n = |K|; n < 3: stop; m = osum(v) / (float)n; d_s = v_s - m; q = osum(d_s * d_s);
+ *                                   var = q / (float)n; tl = kl2 * var; th = kh2 * var; s leaves when
+ *                                   (d_s < 0 && d_s * d_s > tl) || (d_s > 0 && d_s * d_s > th).  A pass that would remove nothing
+ *                                   stops; one that would remove every kept sample removes none and stops.  The statistics are
+ *                                   unweighted.  A NaN or inf among the kept values makes every comparison false: nothing leaves
+ *                           result  osum(w_s * v_s) / osum(w_s) over K; `kept` = |K|, `coverage` = c; c == 0: `empty`, kept 0.
+ *                                   Without weights w_s = 1.0f: with nothing rejected (TRIM 0, 0; SIGMA with iters 0) the plane is
+ *                                   SIFTMI_STACK_MEAN's bit for bit
+ *                         n samples cannot hold a z-score above (n - 1) / sqrt(n): kappa 3 rejects nothing below 11 live frames.
+ *                         TRIM is the rule for short stacks.
+ *   images, maps, fills, mode, out, coverage, kernel_ms   as for siftmi_batch_stack
+ *   kept         OH x OW int32 where `out` lives, or NULL.  A host result is staged as the plane, the coverage and the kept counts
+ *   weights      n floats, each finite and > 0, or NULL for 1.0f
+ *   reject       SIFTMI_STACK_TRIM (n_low, n_high are used) or SIFTMI_STACK_SIGMA (kappa_low, kappa_high, iters are used); the
+ *                parameters of the other rule are still checked
+ * One launch, one synchronisation; device pointers are ordered after the caller's streams as everywhere.  An empty output launches
+ * nothing and returns 0.  n_images == 0 with a non-empty output gives `empty` and zeros in both counts.  SIFTMI_EINVAL, nothing
+ * launched: everything siftmi_batch_stack refuses, n_images > 64, an unknown `reject`, n_low < 0, n_high < 0 or n_low + n_high > 63, a
+ * kappa that is NaN or <= 0 (+inf is allowed and switches its side off), iters < 0, a weight that is not finite and > 0. */
+#define SIFTMI_STACK_TRIM 0
+#define SIFTMI_STACK_SIGMA 1
+#define SIFTMI_STACK_CLIP_MAX 64
+int siftmi_batch_stack_clip(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
+                            float *out, int32_t *coverage /* may be null */, int32_t *kept /* may be null */,
+                            int32_t out_is_device, int32_t out_width, int32_t out_height,
+                            const float *maps /* n x 6 */, const float *fills /* n */, const float *weights /* n, or null = 1.0f */,
+                            int32_t mode, int32_t reject, int32_t n_low, int32_t n_high, float kappa_low, float kappa_high,
+                            int32_t iters, float empty, double *kernel_ms);
 
 /* ---- MatchPlan -----------------------------------------------------------------------------
  * siftmi_match_create <- MatchPlan.__init__ (match.py:77-139)

@@ -547,6 +547,46 @@ class LinearAlign(object):
         from .batch import BatchPlan
         if reduce not in BatchPlan.STACK_REDUCERS:
             raise ValueError("reduce must be one of %s, not %r" % (sorted(BatchPlan.STACK_REDUCERS), reduce))
+        return self._stack(images, "stack_batch", lambda bp, frames, matrix, offset, fills: dict(zip(("stack", "coverage"), bp.stack_batch(
+            frames, matrix, offset, fills, out_shape=self.outshape, mode=1, reduce=reduce, empty=empty, coverage=True, out=out))),
+            max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes)
+
+    def stack_clip(self, images, reject="sigma", trim=(0, 1), kappa=(3.0, 3.0), iters=3, weights=None, max_shift=None, expected_shift=None,
+                   shift_only=False, robust=False, robust_tol=3.0, robust_hyp=2048, match_ratio=None, empty=numpy.nan, return_all=False,
+                   out="host", lanes=None):
+        """``stack`` with an outlier rejection in front of the mean (extension): the estimate of every
+        frame is ``stack``'s and the warp is ``BatchPlan.stack_clip_batch``, which per output pixel drops samples by the chosen rule
+        and returns the weighted mean of the rest, in the launch that samples the frames.  At most 64 frames; greyscale aligners
+        only.  The mean keeps every zinger and the median gives up most of the stack's signal-to-noise; this keeps every sample
+        that is not an outlier.
+
+        ``reject="trim"`` drops the ``trim[1]`` largest and the ``trim[0]`` smallest live samples of a pixel (the largest first, and
+        never the last sample); ``reject="sigma"`` drops, in at most `iters` passes, what lies more than ``kappa[0]`` standard
+        deviations below or ``kappa[1]`` above the mean of the kept samples -- see ``BatchPlan.stack_clip_batch`` for both rules to
+        the last bit.  n samples cannot hold a z-score above ``(n - 1) / sqrt(n)``: ``kappa = 3`` rejects nothing below 11 live
+        frames.  ``trim`` is the rule for short stacks.
+
+        :param images: as for ``align_batch``; at most 64 frames
+        :param reject, trim, kappa, iters, weights: as for ``BatchPlan.stack_clip_batch``
+        :param max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, empty, out, lanes: as for ``stack``
+        :param return_all: return ``stack``'s dict with ``kept`` beside ``coverage``: the (OH, OW) int32 number of frames that
+                       survived in each pixel
+        :return: the combined image (OH, OW), or the dict
+        """
+        if self.RGB:
+            raise RuntimeError("stack_clip combines float32 frames; an RGB aligner has no stack reduction")
+        from .batch import BatchPlan
+        BatchPlan._clip_args(reject, trim, kappa, iters, weights)
+        return self._stack(images, "stack_clip_batch", lambda bp, frames, matrix, offset, fills: dict(zip(
+            ("stack", "coverage", "kept"), bp.stack_clip_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, reject=reject,
+                                                               trim=trim, kappa=kappa, iters=iters, weights=weights, empty=empty, counts=True,
+                                                               out=out))),
+            max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes)
+
+    def _stack(self, images, event, reduce, max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all,
+               out, lanes):
+        """the body of ``stack`` and ``stack_clip``: the estimate of every frame, then ``reduce(bp, frames, matrix, offset, fills)``,
+        which returns the dict of the reduction's planes, ``stack`` first; `event` names the profile event"""
         if out not in ("host", "device"):
             raise ValueError("out must be 'host' or 'device', not %r" % (out,))
         if max_shift is None:
@@ -560,14 +600,12 @@ class LinearAlign(object):
         with self.sem:
             bp = self._batch_plan(lanes)
             frames, matrix, offset, mode, fills, rest = self._estimate_batch(bp, images, matcher, shift_only, robust, robust_tol, robust_hyp)
-            plane, cover = bp.stack_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, reduce=reduce, empty=empty,
-                                          coverage=True, out=out)
+            res = reduce(bp, frames, matrix, offset, fills)
             self.last_stack_ms = bp.last_stack_ms
             if self.profile:
-                self.events.append(("stack_batch", StageEvent(bp.last_stack_ms)))
+                self.events.append((event, StageEvent(bp.last_stack_ms)))
             if not return_all:
-                return plane
-            res = {"stack": plane, "coverage": cover}
+                return res["stack"]
             res.update(rest())
             return res
 

@@ -388,6 +388,101 @@ class BatchPlan(SiftPlan):
         del keep
         return (plane, cover) if coverage else plane
 
+    #: frames ``stack_clip_batch`` may take (SIFTMI_STACK_CLIP_MAX)
+    STACK_CLIP_MAX = 64
+    #: the rejection rules of ``stack_clip_batch`` and their codes in include/siftmi.h
+    STACK_REJECTS = {"trim": 0, "sigma": 1}
+
+    @classmethod
+    def _clip_args(cls, reject, trim, kappa, iters, weights):
+        """The rejection parameters of ``stack_clip_batch`` checked as the library checks them: ``(code, n_low, n_high, kappa_low,
+        kappa_high, iters, weights)`` with `weights` None or a contiguous float32 vector (its length is the caller's to check)."""
+        if reject not in cls.STACK_REJECTS:
+            raise ValueError("reject must be one of %s, not %r" % (sorted(cls.STACK_REJECTS), reject))
+        try:
+            n_low, n_high = (int(v) for v in trim)
+            kl, kh = (float(numpy.float32(v)) for v in kappa)
+        except TypeError:
+            raise ValueError("trim must be (n_low, n_high) and kappa (kappa_low, kappa_high)")
+        if (n_low, n_high) != tuple(trim):
+            raise ValueError("trim takes whole numbers, not %r" % (trim,))
+        if n_low < 0 or n_high < 0 or n_low + n_high > cls.STACK_CLIP_MAX - 1:
+            raise ValueError("trim %r: each count must be >= 0 and their sum at most %d" % (trim, cls.STACK_CLIP_MAX - 1))
+        if not (kl > 0 and kh > 0):
+            raise ValueError("kappa %r: each must be > 0 (inf switches its side off)" % (kappa,))
+        if int(iters) != iters or iters < 0:
+            raise ValueError("iters must be a whole number >= 0, not %r" % (iters,))
+        if weights is not None:
+            weights = numpy.ascontiguousarray(weights, numpy.float32)
+            if weights.ndim != 1:
+                raise ValueError("weights must be one value per frame, not shape %s" % (weights.shape,))
+            if not (numpy.isfinite(weights) & (weights > 0)).all():
+                raise ValueError("every weight must be finite and > 0")
+        return cls.STACK_REJECTS[reject], n_low, n_high, kl, kh, int(iters), weights
+
+    def stack_clip_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, reject="sigma", trim=(0, 1), kappa=(3.0, 3.0),
+                         iters=3, weights=None, empty=numpy.nan, counts=False, out="host"):
+        """Warp S <= 64 float32 frames as ``stack_batch`` does and reduce them to ONE plane in the same launch: per output pixel the
+        weighted mean of the live samples that survive an outlier rejection (``siftmi_batch_stack_clip``; DESIGN.md section 7 row
+        18).  Samples ``v_s``, live frames and coverage ``c`` are ``stack_batch``'s; everything is float32 with one rounding per
+        operation, sums run over the kept frames in the order of the stack and start with their first value.
+
+        * ``reject="trim"``, ``trim=(n_low, n_high)``: the live samples are ordered by value (the total order of float32 that
+          ``reduce="median"`` uses; equal values by frame index); with ``h = min(n_high, c - 1)`` and ``l = min(n_low, c - 1 - h)`` the
+          `h` largest and the `l` smallest are dropped.  At least one sample stays and the high side is served first; a positive NaN
+          sorts above +inf and goes with the high side.
+        * ``reject="sigma"``, ``kappa=(kappa_low, kappa_high)``, at most `iters` passes.  A pass over the n kept samples: stop when
+          ``n < 3``; ``m = sum(v) / n``, ``d_s = v_s - m``, ``var = sum(d_s * d_s) / n``; sample s is dropped when
+          ``d_s < 0 and d_s * d_s > kappa_low**2 * var`` or ``d_s > 0 and d_s * d_s > kappa_high**2 * var``.  A pass that would drop
+          nothing ends the iteration; a pass that would drop every sample drops none and ends it.  The statistics are unweighted.
+          A NaN or an infinity among the kept samples makes every comparison false: nothing is dropped.  ``kappa = inf``
+          switches its side off.
+        * the result is ``sum(w_s * v_s) / sum(w_s)`` over the kept samples, `empty` where no frame is live.  Without `weights`
+          every ``w_s`` is 1: with nothing rejected (``trim=(0, 0)``, or ``iters=0``) the plane is ``stack_batch(reduce="mean")``'s
+          bit for bit.
+
+        n samples cannot hold a z-score above ``(n - 1) / sqrt(n)``: ``kappa = 3`` rejects nothing below 11 live frames.  ``trim``
+        is the rule for short stacks.  Greyscale plans only.
+
+        :param images, matrices, offsets, fills, out_shape, mode: as for ``transform_batch``; at most 64 frames
+        :param reject: ``"sigma"`` or ``"trim"``; the parameters of the other rule are still checked
+        :param trim: (n_low, n_high), each >= 0, their sum at most 63
+        :param kappa: (kappa_low, kappa_high), each > 0; ``inf`` is allowed
+        :param iters: passes of the sigma rule at most, >= 0
+        :param weights: None, or S values, each finite and > 0
+        :param empty: the value of a pixel that no frame covers
+        :param counts: also return the number of live frames and of kept frames of every pixel
+        :param out: ``"host"``: numpy arrays; ``"device"``: torch tensors on the plan's device
+        :return: the (OH, OW) float32 plane, or ``(plane, coverage, kept)`` with two (OH, OW) int32 planes
+        """
+        if self.RGB:
+            raise RuntimeError("stack_clip_batch reduces float32 frames; an RGB plan has no stack reduction")
+        code, n_low, n_high, kl, kh, iters, w = self._clip_args(reject, trim, kappa, iters, weights)
+        ptrs, n, is_dev, keep, maps, f, oh, ow = self._warp_args(images, matrices, offsets, fills, out_shape, out)
+        if n > self.STACK_CLIP_MAX:
+            raise ValueError("a clipped mean takes at most %d frames, not %d" % (self.STACK_CLIP_MAX, n))
+        if w is not None and w.shape != (n,):
+            raise ValueError("weights must be one value per frame (%d), not shape %s" % (n, w.shape))
+        if out == "device":
+            import torch
+            dev = torch.device("cuda", self.device)
+            plane = torch.empty((oh, ow), dtype=torch.float32, device=dev)
+            cover, kept = ((torch.empty((oh, ow), dtype=torch.int32, device=dev) for _ in range(2)) if counts else (None, None))
+            pptr, cptr, kptr = plane.data_ptr(), (cover.data_ptr() if counts else None), (kept.data_ptr() if counts else None)
+        else:
+            plane = self._host_result((oh, ow), numpy.float32)
+            cover, kept = ((self._host_result((oh, ow), numpy.int32) for _ in range(2)) if counts else (None, None))
+            pptr, cptr, kptr = plane.ctypes.data, (cover.ctypes.data if counts else None), (kept.ctypes.data if counts else None)
+        ms = C.c_double(0)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_batch_stack_clip(self._handle, ptrs, n, is_dev, pptr, cptr, kptr, int(out == "device"), ow, oh,
+                                                          maps.ctypes.data, f.ctypes.data, None if w is None else w.ctypes.data, int(mode),
+                                                          code, n_low, n_high, C.c_float(kl), C.c_float(kh), iters, C.c_float(empty),
+                                                          C.byref(ms)))
+        self.last_stack_ms = ms.value
+        del keep
+        return (plane, cover, kept) if counts else plane
+
     def minmax(self):
         raise RuntimeError("BatchPlan keeps no per-frame min/max; use SiftPlan")
 

@@ -24,6 +24,7 @@
 #include "k_align.hpp"
 #include "k_align_batch.hpp"
 #include "k_stack.hpp"
+#include "k_stack_clip.hpp"
 #include "k_pyramid.hpp"
 #include "k_tail.hpp"
 #include "siftmath.hpp"
@@ -2078,11 +2079,16 @@ int warp_begin(siftmi_batch *b, const void *const *images, int32_t n_images, int
 }
 
 // After the launch (bracketed by ev_wa / ev_wb): a host result copied back from the staging -- `bytes0` to `host0`, then the
-// `bytes1` behind them to `host1` when there is a second piece --, the one synchronisation, and kernel_ms from the event pair.
-int warp_end(siftmi_batch *b, const WarpIo &io, void *host0, size_t bytes0, void *host1, size_t bytes1, double *kernel_ms) {
+// `bytes1` behind them to `host1` when there is a second piece and the `bytes2` behind those to `host2` when there is a third
+// (a piece whose pointer is null is skipped, the ones behind it stay where they are) --, the one synchronisation, and kernel_ms
+// from the event pair.
+int warp_end(siftmi_batch *b, const WarpIo &io, void *host0, size_t bytes0, void *host1, size_t bytes1, double *kernel_ms,
+             void *host2 = nullptr, size_t bytes2 = 0) {
     if (host0 && bytes0) {
         hipError_t e = hipMemcpyAsync(host0, io.dst, bytes0, hipMemcpyDeviceToHost, io.stream);
         if (e == hipSuccess && host1 && bytes1) e = hipMemcpyAsync(host1, (const uint8_t *)io.dst + bytes0, bytes1, hipMemcpyDeviceToHost, io.stream);
+        if (e == hipSuccess && host2 && bytes2)
+            e = hipMemcpyAsync(host2, (const uint8_t *)io.dst + bytes0 + bytes1, bytes2, hipMemcpyDeviceToHost, io.stream);
         if (e != hipSuccess) { (void)hipStreamSynchronize(io.stream); return fail(SIFTMI_EDEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e)); }
     }
     HIPCHK(hipStreamSynchronize(io.stream));       // (the pinned table and the caller's frames are free again from here on)
@@ -2107,6 +2113,18 @@ void launch_stack(hipStream_t st, int reduce, const WarpFrame *frames, int S, fl
         hipLaunchKernelGGL(stack_reduce_kernel<true>, grid, block, 0, st, frames, S, out, coverage, W, H, OW, OH, empty);
     else
         hipLaunchKernelGGL(stack_reduce_kernel<false>, grid, block, 0, st, frames, S, out, coverage, W, H, OW, OH, empty);
+}
+
+// The one launch site of the clipped stack reduction (k_stack_clip.hpp): S <= 64 frames to one OH x OW plane and, unless null, its
+// coverage and kept counts.  Dynamic LDS is the S x 256 samples of a block.  S == 0 fills the plane with `empty` and both counts with 0.
+void launch_stack_clip(hipStream_t st, int reject, const WarpFrame *frames, int S, const StackClipArgs &p, float *out, int32_t *coverage,
+                       int32_t *kept, int W, int H, int OW, int OH, float empty) {
+    const dim3 grid((unsigned)((OW + 63) / 64), (unsigned)((OH + 3) / 4)), block(64, 4);
+    const size_t lds = (size_t)S * 256 * sizeof(float);
+    if (reject == SIFTMI_STACK_TRIM)
+        hipLaunchKernelGGL(stack_clip_kernel<SIFT_STACK_TRIM>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
+    else
+        hipLaunchKernelGGL(stack_clip_kernel<SIFT_STACK_SIGMA>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
 }
 }  // namespace
 
@@ -2174,6 +2192,55 @@ int siftmi_batch_stack(siftmi_batch *b, const void *const *images, int32_t n_ima
     launch_stack(io.stream, n_images ? reduce : SIFTMI_STACK_SUM, (const WarpFrame *)b->warp_tab, n_images, (float *)io.dst, cov, io.W, io.H, OW, OH, empty);
     hipEventRecord(b->ev_wb, io.stream);
     return warp_end(b, io, out_is_device ? nullptr : out, plane, coverage, plane, kernel_ms);
+}
+
+// S <= 64 frames warped, outliers rejected per pixel and the survivors averaged in one launch (k_stack_clip.hpp).  Without a frame
+// the kernel itself is the fill path, as for siftmi_batch_stack.
+int siftmi_batch_stack_clip(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, float *out,
+                            int32_t *coverage, int32_t *kept, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps,
+                            const float *fills, const float *weights, int32_t mode, int32_t reject, int32_t n_low, int32_t n_high,
+                            float kappa_low, float kappa_high, int32_t iters, float empty, double *kernel_ms) {
+    if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (n_images < 0) return fail(SIFTMI_EINVAL, "negative image count");
+    static_assert(SIFTMI_STACK_CLIP_MAX == SIFT_STACK_CLIP_MAX && SIFTMI_STACK_TRIM == SIFT_STACK_TRIM && SIFTMI_STACK_SIGMA == SIFT_STACK_SIGMA,
+                  "siftmi.h and k_stack_clip.hpp disagree");
+    if (n_images > SIFTMI_STACK_CLIP_MAX) return fail(SIFTMI_EINVAL, "a clipped mean of %d frames: more than %d", n_images, SIFTMI_STACK_CLIP_MAX);
+    if (reject != SIFTMI_STACK_TRIM && reject != SIFTMI_STACK_SIGMA) return fail(SIFTMI_EINVAL, "reject must be 0 (trim) or 1 (sigma), got %d", reject);
+    if (n_low < 0 || n_high < 0 || (int64_t)n_low + n_high > SIFTMI_STACK_CLIP_MAX - 1)
+        return fail(SIFTMI_EINVAL, "n_low %d, n_high %d: each must be >= 0 and their sum at most %d", n_low, n_high, SIFTMI_STACK_CLIP_MAX - 1);
+    if (!(kappa_low > 0.0f) || !(kappa_high > 0.0f)) return fail(SIFTMI_EINVAL, "kappa_low %g, kappa_high %g: each must be > 0 (inf allowed)", kappa_low, kappa_high);
+    if (iters < 0) return fail(SIFTMI_EINVAL, "negative iteration count");
+    if (OW < 0 || OH < 0) return fail(SIFTMI_EINVAL, "negative output shape");
+    if (OH > 4 * 65535) return fail(SIFTMI_EINVAL, "output height %d: more than %d rows (4 per grid row)", OH, 4 * 65535);
+    if (!b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8) return fail(SIFTMI_EINVAL, "a batch created for RGB8 frames has no stack reduction");
+    const bool nothing = OW == 0 || OH == 0;
+    if (n_images > 0 && (!images || !maps || !fills)) return fail(SIFTMI_EINVAL, "null argument");
+    if (!nothing && !out) return fail(SIFTMI_EINVAL, "null output");
+    for (int32_t i = 0; i < n_images; i++) if (!images[i]) return fail(SIFTMI_EINVAL, "null image %d", i);
+    StackClipArgs p;
+    for (int i = 0; i < SIFT_STACK_CLIP_MAX; i++) p.w[i] = 1.0f;
+    for (int32_t i = 0; weights && i < n_images; i++) {
+        if (!(weights[i] > 0.0f) || std::isinf(weights[i])) return fail(SIFTMI_EINVAL, "weight %d is %g: must be finite and > 0", i, weights[i]);
+        p.w[i] = weights[i];
+    }
+    p.n_low = n_low; p.n_high = n_high; p.kappa_low = kappa_low; p.kappa_high = kappa_high; p.iters = iters;
+    if (kernel_ms) *kernel_ms = 0;
+    if (nothing || b->lanes.empty()) return SIFTMI_OK;
+    const size_t plane = (size_t)OW * OH * sizeof(float);
+    const bool counts = coverage || kept;
+    WarpIo io;
+    int rc = warp_begin(b, images, n_images, images_are_device, sizeof(float), out, out_is_device, plane * (counts ? 3 : 1), maps, fills, mode, &io);
+    if (rc) return rc;
+    // a host result: the plane, then the coverage, then the kept counts, in the batch's staging
+    int32_t *cov = coverage, *kep = kept;
+    if (!out_is_device) {
+        cov = coverage ? reinterpret_cast<int32_t *>((uint8_t *)io.dst + plane) : nullptr;
+        kep = kept ? reinterpret_cast<int32_t *>((uint8_t *)io.dst + 2 * plane) : nullptr;
+    }
+    hipEventRecord(b->ev_wa, io.stream);
+    launch_stack_clip(io.stream, reject, (const WarpFrame *)b->warp_tab, n_images, p, (float *)io.dst, cov, kep, io.W, io.H, OW, OH, empty);
+    hipEventRecord(b->ev_wb, io.stream);
+    return warp_end(b, io, out_is_device ? nullptr : out, plane, coverage, plane, kernel_ms, kept, plane);
 }
 
 int siftmi_plan_records_device(const siftmi_plan *p, const siftmi_keypoint **records, int64_t *count) {
