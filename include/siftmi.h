@@ -341,6 +341,52 @@ int siftmi_batch_stack_clip(siftmi_batch *batch, const void *const *images, int3
                             const float *maps /* n x 6 */, const float *fills /* n */, const float *weights /* n, or null = 1.0f */,
                             int32_t mode, int32_t reject, int32_t n_low, int32_t n_high, float kappa_low, float kappa_high,
                             int32_t iters, float empty, double *kernel_ms);
+/* A second sampler for the whole warp family (extension; DESIGN.md section 7 row 19, restated in numpy by
+ * tests/warp_cubic_ref.py; kernels in csrc/k_warp_cubic.hpp, k_stack.hpp and k_stack_clip.hpp).  Each _ex entry takes its
+ * parent's arguments plus `interp` behind `mode`; the parent IS the _ex call with SIFTMI_INTERP_MODE -- one body: staging,
+ * ordering after the caller's streams, limits and error states are the parent's.
+ *   SIFTMI_INTERP_MODE   what `mode` says: the parent's result, bit for bit
+ *   SIFTMI_INTERP_CUBIC  Catmull-Rom bicubic (4 x 4 taps, a = -1/2) on float32 frames.  Binary32; every product, sum and
+ *                        difference rounded on its own in the order written (the build's -ffp-contract=off is part of this):
+ *     (ty, tx)   as siftmi_plan_transform: ty = (m0*y + m1*x) + off0, tx = (m2*y + m3*x) + off1
+ *     live       0 <= tx && tx < (float)W + -0.5f && 0 <= ty && ty < (float)H + -0.5f      (siftmi_batch_stack's live_s, unchanged;
+ *                false for a non-finite tx or ty; no index is formed unless live)
+ *     !live      out = fill
+ *     xp = (int)tx, yp = (int)ty;  fx = tx - (float)xp,  fy = ty - (float)yp
+ *     columns    c_k = clamp(xp - 1 + k, 0, W - 1),  rows r_j = clamp(yp - 1 + j, 0, H - 1),  j, k = 0..3   (edge pixels repeat;
+ *                `fill` is never mixed into a live sample)
+ *     weights    w0 = ((-0.5f*f + 1.0f)*f - 0.5f)*f        w1 = ((1.5f*f - 2.5f)*f)*f + 1.0f
+ *                w2 = ((-1.5f*f + 2.0f)*f + 0.5f)*f        w3 = ((0.5f*f - 0.5f)*f)*f            (f = fx for wx, fy for wy)
+ *     rows       R_j = ((wx0*p[r_j][c_0] + wx1*p[r_j][c_1]) + wx2*p[r_j][c_2]) + wx3*p[r_j][c_3]
+ *     value      out = ((wy0*R_0 + wy1*R_1) + wy2*R_2) + wy3*R_3
+ *   At f = 0 the weights are exactly (-0, 1, 0, -0): an integer shift of a finite frame returns its pixels bit for bit, except
+ *   that -0.0 becomes +0.0.  At f = 1/4, 1/2, 3/4 they are exact (k / 128; (-1, 9, 9, -1) / 16); their sum is 1 within 2.4e-7.
+ *   Zero weights still multiply: a NaN anywhere in the 4 x 4 footprint makes the sample NaN, and so does an inf (0 * inf, inf - inf)
+ *   unless every weight it meets is non-zero -- at an integer shift only the sample ON an inf pixel stays inf; a NaN the
+ *   arithmetic creates is the device's default NaN, a positive one.  The live set is the bilinear warp's non-fill set: coverage, `empty` and `kept`
+ *   of a stack mean the same under both samplers; v_s of the two stack entries is the cubic sample, every rule behind it is
+ *   unchanged.  A cubic sample can overshoot the range of its taps.
+ * SIFTMI_EINVAL, nothing launched: everything the parent refuses, an unknown `interp`, SIFTMI_INTERP_CUBIC with mode != 1
+ * (reserved) or with RGB8 frames (channels == 3, or a batch created for RGB8). */
+#define SIFTMI_INTERP_MODE 0
+#define SIFTMI_INTERP_CUBIC 1
+int siftmi_plan_transform_ex(siftmi_plan *plan, const void *image, int32_t image_is_device, int32_t channels, void *out,
+                             int32_t out_is_device, int32_t out_width, int32_t out_height, const float *matrix /*[4]*/,
+                             const float *offset /*[2]*/, float fill, int32_t mode, int32_t interp, double *kernel_ms);
+int siftmi_batch_transform_ex(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
+                              int32_t channels, void *out, int32_t out_is_device, int32_t out_width, int32_t out_height,
+                              const float *maps /* n x 6 */, const float *fills /* n */, int32_t mode, int32_t interp,
+                              double *kernel_ms);
+int siftmi_batch_stack_ex(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
+                          float *out /* OH x OW */, int32_t *coverage /* may be null */, int32_t out_is_device,
+                          int32_t out_width, int32_t out_height, const float *maps /* n x 6 */, const float *fills /* n */,
+                          int32_t mode, int32_t interp, int32_t reduce, float empty, double *kernel_ms);
+int siftmi_batch_stack_clip_ex(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
+                               float *out, int32_t *coverage /* may be null */, int32_t *kept /* may be null */,
+                               int32_t out_is_device, int32_t out_width, int32_t out_height,
+                               const float *maps /* n x 6 */, const float *fills /* n */, const float *weights /* n, or null */,
+                               int32_t mode, int32_t interp, int32_t reject, int32_t n_low, int32_t n_high, float kappa_low,
+                               float kappa_high, int32_t iters, float empty, double *kernel_ms);
 
 /* ---- MatchPlan -----------------------------------------------------------------------------
  * siftmi_match_create <- MatchPlan.__init__ (match.py:77-139)

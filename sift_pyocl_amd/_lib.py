@@ -12,6 +12,42 @@ LIB_PATH = os.path.join(HERE, "libsiftmi.so")
 
 OK, EINVAL, ENOMEM, EDEVICE, ECAPACITY = 0, -1, -2, -3, -4
 METRIC_L1, METRIC_L2SQ = 0, 1
+INTERP_MODE, INTERP_CUBIC = 0, 1             # SIFTMI_INTERP_*
+INTERPS = {None: INTERP_MODE, "linear": INTERP_MODE, "cubic": INTERP_CUBIC}
+
+
+def interp_code(interp, mode=1, rgb=False):
+    """The SIFTMI_INTERP_* code of the keyword ``interp`` of the warp methods, checked as the library checks it, before any
+    launch: ``None`` and ``"linear"`` are what `mode` says; ``"cubic"`` takes ``mode == 1`` and float32 frames only."""
+    if not (interp is None or isinstance(interp, str)) or interp not in INTERPS:
+        raise ValueError("interp must be None, 'linear' or 'cubic', not %r" % (interp,))
+    code = INTERPS[interp]
+    if code == INTERP_CUBIC and int(mode) != 1:
+        raise ValueError("interp='cubic' takes mode=1 only (other values are reserved), not %r" % (mode,))
+    if code == INTERP_CUBIC and rgb:
+        raise ValueError("interp='cubic' takes float32 frames; an RGB plan has no cubic sampler")
+    return code
+
+
+def interp_keyword(impl):
+    """Decorator that gives a warp method the keyword ``interp`` without a change to its parameter list, which the tests of the
+    rows that introduced it pin: without the keyword the method runs as it is; with it, the call's arguments are bound to the
+    method's own signature and handed to ``getattr(self, impl)`` with ``interp`` behind them."""
+    import functools
+    import inspect
+
+    def decorate(method):
+        sig = inspect.signature(method)
+
+        @functools.wraps(method)
+        def call(self, *args, interp=None, **kwargs):
+            if interp is None:
+                return method(self, *args, **kwargs)
+            bound = sig.bind(self, *args, **kwargs)
+            bound.apply_defaults()
+            return getattr(self, impl)(*bound.args[1:], **bound.kwargs, interp=interp)
+        return call
+    return decorate
 
 DTYPE_CODES = {"float32": 0, "uint8": 1, "uint16": 2, "uint32": 3, "uint64": 4, "int32": 5, "int64": 6,
                "float64": 7, "rgb8": 8}
@@ -90,6 +126,16 @@ _SIGNATURES = {
     "siftmi_batch_stack_clip": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_float, C.c_float, C.c_int32, C.c_float, C.POINTER(C.c_double)]),
+    # the _ex forms of the warp family: the parent's arguments with `interp` behind `mode`
+    "siftmi_plan_transform_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "siftmi_batch_transform_ex": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "siftmi_batch_stack_ex": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_double)]),
+    "siftmi_batch_stack_clip_ex": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float, C.POINTER(C.c_double)]),
     "siftmi_match_set_roi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "siftmi_match_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

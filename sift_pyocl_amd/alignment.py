@@ -150,8 +150,14 @@ class LinearAlign(object):
         return kp[inside]
 
     # ------------------------------------------------------------------ device warp
-    def transform(self, matrix, offset, image=None, fill=None, mode=1):
-        """Affine warp on the device (transform.cl).  image=None warps the image staged by the last keypoints()."""
+    def transform(self, matrix, offset, image=None, fill=None, mode=1, interp=None):
+        """Affine warp on the device (transform.cl).  image=None warps the image staged by the last keypoints().
+
+        :param interp: (extension) None or ``"linear"``: what `mode` says, the reference's 2 x 2
+                       bilinear kernel for ``mode=1``; ``"cubic"``: the Catmull-Rom bicubic sampler (4 x 4 taps, a = -1/2, edge
+                       pixels repeated, the same fill region).  Greyscale aligners and ``mode=1`` only: ``ValueError`` otherwise
+        """
+        interp = _lib.interp_code(interp, mode, self.RGB)
         matrix = numpy.ascontiguousarray(matrix, numpy.float32).reshape(4)
         offset = numpy.ascontiguousarray(offset, numpy.float32).reshape(2)
         if fill is None:
@@ -175,9 +181,9 @@ class LinearAlign(object):
             assert image.shape[:2] == self.shape
             ptr = image.ctypes.data
         ms = C.c_double(0)
-        _lib.check(_lib.lib().siftmi_plan_transform(self.sift._handle, ptr, 0, 3 if self.RGB else 1, out.ctypes.data, 0,
-                                                    self.outshape[1], self.outshape[0], matrix.ctypes.data, offset.ctypes.data,
-                                                    C.c_float(fill), int(mode), C.byref(ms)))
+        _lib.check(_lib.lib().siftmi_plan_transform_ex(self.sift._handle, ptr, 0, 3 if self.RGB else 1, out.ctypes.data, 0,
+                                                       self.outshape[1], self.outshape[0], matrix.ctypes.data, offset.ctypes.data,
+                                                       C.c_float(fill), int(mode), interp, C.byref(ms)))
         self.last_transform_ms = ms.value
         if self.profile:
             self.events.append(("transform", StageEvent(ms.value)))
@@ -230,7 +236,7 @@ class LinearAlign(object):
     # ------------------------------------------------------------------ public entry
     def align(self, img, shift_only=False, return_all=False, double_check=False, relative=False, orsa=False,
               robust=False, robust_tol=3.0, robust_hyp=2048, max_shift=None, estimate="host", match_metric="l1", match_ratio=None,
-              median="host"):
+              median="host", interp=None):
         """Align `img` on the reference image.
 
         :param img: image to align (same shape as the reference)
@@ -272,8 +278,11 @@ class LinearAlign(object):
                        for value, and without ``return_all`` the matched positions are not gathered on the host at all.  The
                        host path is taken all the same under ``double_check`` and when ORSA filtered the matches.
                        ``estimate=`` keeps its meaning; ``shift_only`` with ``estimate="device"`` alone stays the host path.
+        :param interp: (extension) the sampler of the final warp, as for ``transform``: None or ``"linear"`` (bilinear) or
+                       ``"cubic"`` (greyscale aligners only); the estimate is unchanged
         :return: the aligned image, the dict, or None when no keypoint matches
         """
+        _lib.interp_code(interp, 1, self.RGB)
         if median not in ("host", "device"):
             raise ValueError("median must be 'host' or 'device', not %r" % (median,))
         if estimate not in ("host", "device"):
@@ -384,7 +393,7 @@ class LinearAlign(object):
             if relative:
                 self._set_reference(kp)             # this frame becomes the reference of the next one
                 matrix, offset = self._chain_relative(matrix, offset)
-            result = self.transform(matrix, offset, image=None, fill=self.sift.minmax()[0], mode=1)
+            result = self.transform(matrix, offset, image=None, fill=self.sift.minmax()[0], mode=1, interp=interp)
 
         if not return_all:
             return result
@@ -455,6 +464,7 @@ class LinearAlign(object):
             stack[i].copy_(host)
         return [stack[i] for i in range(len(images))]
 
+    @_lib.interp_keyword("_align_batch_interp")
     def align_batch(self, images, shift_only=False, robust=False, robust_tol=3.0, robust_hyp=2048, match_ratio=None, return_all=False,
                     out="host", lanes=None):
         """Align a stack of S frames on the reference image in one pass (extension): every stage runs
@@ -485,11 +495,18 @@ class LinearAlign(object):
                        frame, ``pair_counts``, and under ``robust`` ``inliers``, the bool (M,) mask over ``pairs`` that was used
         :param out: ``"host"``: the stack is a numpy array; ``"device"``: a torch tensor on the aligner's device
         :param lanes: lanes of the ``BatchPlan`` (created on first use); None: its default for the frame size
+        :param interp: (keyword only) the sampler of the warp, as for ``transform``: None or
+                       ``"linear"`` (bilinear) or ``"cubic"`` (greyscale aligners only); the estimate is unchanged
         :return: the aligned stack (S, OH, OW[, 3]), or the dict
         """
-        return self._align_batch(images, lambda ref, records, counts: self.match.match_batch(ref, None, records, counts, ratio=match_ratio, out="device"),
-                                 shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes)
+        return self._align_batch_interp(images, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes)
 
+    def _align_batch_interp(self, images, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes, interp=None):
+        """the body of ``align_batch``"""
+        return self._align_batch(images, lambda ref, records, counts: self.match.match_batch(ref, None, records, counts, ratio=match_ratio, out="device"),
+                                 shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes, interp)
+
+    @_lib.interp_keyword("_align_batch_window_interp")
     def align_batch_window(self, images, max_shift, expected_shift=None, shift_only=False, robust=False, robust_tol=3.0, robust_hyp=2048,
                            match_ratio=None, return_all=False, out="host", lanes=None):
         """``align_batch`` with the windowed matcher (extension): the match stage is
@@ -509,16 +526,23 @@ class LinearAlign(object):
                        the expected shift), a scalar or an (x, y) pair; ``inf`` is allowed.  Required
         :param expected_shift: None (no displacement expected), one ``(sx, sy)`` for all frames or an (S, 2) array with one per
                        frame, in (x, y) order: where a frame's keypoints are expected relative to their partners in the reference
-        :param shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes: as for ``align_batch``
+        :param shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes, interp: as for ``align_batch``
         :return: the aligned stack (S, OH, OW[, 3]), or ``align_batch``'s dict
         """
+        return self._align_batch_window_interp(images, max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio,
+                                               return_all, out, lanes)
+
+    def _align_batch_window_interp(self, images, max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio,
+                                   return_all, out, lanes, interp=None):
+        """the body of ``align_batch_window``"""
         if max_shift is None:
             raise ValueError("align_batch_window needs max_shift; without a window the call is align_batch")
         shift = (0.0, 0.0) if expected_shift is None else expected_shift
         return self._align_batch(images, lambda ref, records, counts: self.match.match_window_batch(
             ref, None, records, counts, window=max_shift, window_shift=shift, ratio=match_ratio, out="device"),
-            shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes)
+            shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes, interp)
 
+    @_lib.interp_keyword("_stack_interp")
     def stack(self, images, reduce="mean", max_shift=None, expected_shift=None, shift_only=False, robust=False, robust_tol=3.0,
               robust_hyp=2048, match_ratio=None, empty=numpy.nan, return_all=False, out="host", lanes=None):
         """Align a stack of S frames on the reference image and combine them into ONE image (extension; DESIGN.md section 7 row
@@ -540,17 +564,27 @@ class LinearAlign(object):
         :param return_all: return ``align_batch``'s dict without ``result`` and with ``stack``, the (OH, OW) float32 image, and
                        ``coverage``, the (OH, OW) int32 number of frames that cover each pixel
         :param out: ``"host"``: numpy arrays; ``"device"``: torch tensors on the aligner's device
+        :param interp: (keyword only) the sampler of the warp, as for ``BatchPlan.stack_batch``: None
+                       or ``"linear"`` (bilinear) or ``"cubic"``; estimate, coverage and reducers are unchanged
         :return: the combined image (OH, OW), or the dict
         """
+        return self._stack_interp(images, reduce, max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, empty,
+                                  return_all, out, lanes)
+
+    def _stack_interp(self, images, reduce, max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, empty,
+                      return_all, out, lanes, interp=None):
+        """the body of ``stack``"""
+        _lib.interp_code(interp, 1, self.RGB)
         if self.RGB:
             raise RuntimeError("stack combines float32 frames; an RGB aligner has no stack reduction")
         from .batch import BatchPlan
         if reduce not in BatchPlan.STACK_REDUCERS:
             raise ValueError("reduce must be one of %s, not %r" % (sorted(BatchPlan.STACK_REDUCERS), reduce))
         return self._stack(images, "stack_batch", lambda bp, frames, matrix, offset, fills: dict(zip(("stack", "coverage"), bp.stack_batch(
-            frames, matrix, offset, fills, out_shape=self.outshape, mode=1, reduce=reduce, empty=empty, coverage=True, out=out))),
+            frames, matrix, offset, fills, out_shape=self.outshape, mode=1, reduce=reduce, empty=empty, coverage=True, out=out, interp=interp))),
             max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes)
 
+    @_lib.interp_keyword("_stack_clip_interp")
     def stack_clip(self, images, reject="sigma", trim=(0, 1), kappa=(3.0, 3.0), iters=3, weights=None, max_shift=None, expected_shift=None,
                    shift_only=False, robust=False, robust_tol=3.0, robust_hyp=2048, match_ratio=None, empty=numpy.nan, return_all=False,
                    out="host", lanes=None):
@@ -571,8 +605,16 @@ class LinearAlign(object):
         :param max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, empty, out, lanes: as for ``stack``
         :param return_all: return ``stack``'s dict with ``kept`` beside ``coverage``: the (OH, OW) int32 number of frames that
                        survived in each pixel
+        :param interp: (keyword only) as for ``stack``
         :return: the combined image (OH, OW), or the dict
         """
+        return self._stack_clip_interp(images, reject, trim, kappa, iters, weights, max_shift, expected_shift, shift_only, robust, robust_tol,
+                                       robust_hyp, match_ratio, empty, return_all, out, lanes)
+
+    def _stack_clip_interp(self, images, reject, trim, kappa, iters, weights, max_shift, expected_shift, shift_only, robust, robust_tol,
+                           robust_hyp, match_ratio, empty, return_all, out, lanes, interp=None):
+        """the body of ``stack_clip``"""
+        _lib.interp_code(interp, 1, self.RGB)
         if self.RGB:
             raise RuntimeError("stack_clip combines float32 frames; an RGB aligner has no stack reduction")
         from .batch import BatchPlan
@@ -580,7 +622,7 @@ class LinearAlign(object):
         return self._stack(images, "stack_clip_batch", lambda bp, frames, matrix, offset, fills: dict(zip(
             ("stack", "coverage", "kept"), bp.stack_clip_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, reject=reject,
                                                                trim=trim, kappa=kappa, iters=iters, weights=weights, empty=empty, counts=True,
-                                                               out=out))),
+                                                               out=out, interp=interp))),
             max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all, out, lanes)
 
     def _stack(self, images, event, reduce, max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, return_all,
@@ -668,15 +710,16 @@ class LinearAlign(object):
             return res
         return frames, matrix, offset, mode, fills, rest
 
-    def _align_batch(self, images, matcher, shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes):
+    def _align_batch(self, images, matcher, shift_only, robust, robust_tol, robust_hyp, return_all, out, lanes, interp=None):
         """the body of ``align_batch``: the estimate of every frame, then the warp; ``matcher(ref_list, records, counts)`` returns
         ``(pairs, pair_counts)`` with the pairs on the device"""
         if out not in ("host", "device"):
             raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        _lib.interp_code(interp, 1, self.RGB)
         with self.sem:
             bp = self._batch_plan(lanes)
             frames, matrix, offset, mode, fills, rest = self._estimate_batch(bp, images, matcher, shift_only, robust, robust_tol, robust_hyp)
-            result = bp.transform_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, out=out)
+            result = bp.transform_batch(frames, matrix, offset, fills, out_shape=self.outshape, mode=1, out=out, interp=interp)
             self.last_transform_ms = bp.last_transform_ms
             if self.profile:
                 self.events.append(("transform_batch", StageEvent(bp.last_transform_ms)))

@@ -301,6 +301,7 @@ class BatchPlan(SiftPlan):
                 pass
         return numpy.empty(oshape, odtype)
 
+    @_lib.interp_keyword("_transform_batch")
     def transform_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, out="host"):
         """Affine warp of S frames of the plan's shape in one launch (``siftmi_batch_transform``): frame s of the result is bit
         for bit ``LinearAlign.transform(matrices[s], offsets[s], images[s], fills[s], mode)``.  One synchronisation, one upload of a
@@ -316,8 +317,16 @@ class BatchPlan(SiftPlan):
         :param mode: 1 = bilinear, anything else = the nearest-lower tap
         :param out: ``"host"``: a numpy array (in a pinned block of the library's pool when it fits, as ``LinearAlign.transform``
                     returns it); ``"device"``: a torch tensor on the plan's device
+        :param interp: (keyword only) None or ``"linear"``: what `mode` says; ``"cubic"``: the Catmull-Rom bicubic sampler
+                    (4 x 4 taps, edge pixels repeated; float32 plans and ``mode=1`` only, ``ValueError`` otherwise; DESIGN.md
+                    section 7 row 19).  Frame s is then ``LinearAlign.transform(..., interp="cubic")`` bit for bit
         :return: (S, OH, OW) float32, or (S, OH, OW, 3) uint8
         """
+        return self._transform_batch(images, matrices, offsets, fills, out_shape, mode, out)
+
+    def _transform_batch(self, images, matrices, offsets, fills, out_shape, mode, out, interp=None):
+        """the body of ``transform_batch``"""
+        interp = _lib.interp_code(interp, mode, self.RGB)
         ptrs, n, is_dev, keep, maps, f, oh, ow = self._warp_args(images, matrices, offsets, fills, out_shape, out)
         oshape, odtype = ((n, oh, ow, 3), numpy.uint8) if self.RGB else ((n, oh, ow), numpy.float32)
         if out == "device":
@@ -329,8 +338,8 @@ class BatchPlan(SiftPlan):
             optr = result.ctypes.data
         ms = C.c_double(0)
         with self._sem:
-            _lib.check(_lib.lib().siftmi_batch_transform(self._handle, ptrs, n, is_dev, 3 if self.RGB else 1, optr, int(out == "device"),
-                                                         ow, oh, maps.ctypes.data, f.ctypes.data, int(mode), C.byref(ms)))
+            _lib.check(_lib.lib().siftmi_batch_transform_ex(self._handle, ptrs, n, is_dev, 3 if self.RGB else 1, optr, int(out == "device"),
+                                                            ow, oh, maps.ctypes.data, f.ctypes.data, int(mode), interp, C.byref(ms)))
         self.last_transform_ms = ms.value
         del keep
         return result
@@ -340,6 +349,7 @@ class BatchPlan(SiftPlan):
     #: frames a median may take (SIFTMI_STACK_MEDIAN_MAX)
     STACK_MEDIAN_MAX = 64
 
+    @_lib.interp_keyword("_stack_batch")
     def stack_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, reduce="mean", empty=numpy.nan, coverage=False,
                     out="host"):
         """Warp S float32 frames as ``transform_batch`` does and reduce them to ONE plane in the same launch
@@ -360,8 +370,15 @@ class BatchPlan(SiftPlan):
         :param empty: the value of a pixel that no frame covers
         :param coverage: also return the number of live frames of every pixel
         :param out: ``"host"``: numpy arrays; ``"device"``: torch tensors on the plan's device
+        :param interp: (keyword only) as for ``transform_batch``: ``"cubic"`` samples every frame with the bicubic kernel; live
+                       frames, coverage and every reducer are unchanged
         :return: the (OH, OW) float32 plane, or ``(plane, coverage)`` with the (OH, OW) int32 counts
         """
+        return self._stack_batch(images, matrices, offsets, fills, out_shape, mode, reduce, empty, coverage, out)
+
+    def _stack_batch(self, images, matrices, offsets, fills, out_shape, mode, reduce, empty, coverage, out, interp=None):
+        """the body of ``stack_batch``"""
+        interp = _lib.interp_code(interp, mode, self.RGB)
         if self.RGB:
             raise RuntimeError("stack_batch reduces float32 frames; an RGB plan has no stack reduction")
         if reduce not in self.STACK_REDUCERS:
@@ -381,9 +398,9 @@ class BatchPlan(SiftPlan):
             pptr, cptr = plane.ctypes.data, (cover.ctypes.data if coverage else None)
         ms = C.c_double(0)
         with self._sem:
-            _lib.check(_lib.lib().siftmi_batch_stack(self._handle, ptrs, n, is_dev, pptr, cptr, int(out == "device"), ow, oh,
-                                                     maps.ctypes.data, f.ctypes.data, int(mode), self.STACK_REDUCERS[reduce],
-                                                     C.c_float(empty), C.byref(ms)))
+            _lib.check(_lib.lib().siftmi_batch_stack_ex(self._handle, ptrs, n, is_dev, pptr, cptr, int(out == "device"), ow, oh,
+                                                        maps.ctypes.data, f.ctypes.data, int(mode), interp, self.STACK_REDUCERS[reduce],
+                                                        C.c_float(empty), C.byref(ms)))
         self.last_stack_ms = ms.value
         del keep
         return (plane, cover) if coverage else plane
@@ -420,6 +437,7 @@ class BatchPlan(SiftPlan):
                 raise ValueError("every weight must be finite and > 0")
         return cls.STACK_REJECTS[reject], n_low, n_high, kl, kh, int(iters), weights
 
+    @_lib.interp_keyword("_stack_clip_batch")
     def stack_clip_batch(self, images, matrices, offsets, fills=0.0, out_shape=None, mode=1, reject="sigma", trim=(0, 1), kappa=(3.0, 3.0),
                          iters=3, weights=None, empty=numpy.nan, counts=False, out="host"):
         """Warp S <= 64 float32 frames as ``stack_batch`` does and reduce them to ONE plane in the same launch: per output pixel the
@@ -453,8 +471,15 @@ class BatchPlan(SiftPlan):
         :param empty: the value of a pixel that no frame covers
         :param counts: also return the number of live frames and of kept frames of every pixel
         :param out: ``"host"``: numpy arrays; ``"device"``: torch tensors on the plan's device
+        :param interp: (keyword only) as for ``stack_batch``
         :return: the (OH, OW) float32 plane, or ``(plane, coverage, kept)`` with two (OH, OW) int32 planes
         """
+        return self._stack_clip_batch(images, matrices, offsets, fills, out_shape, mode, reject, trim, kappa, iters, weights, empty, counts, out)
+
+    def _stack_clip_batch(self, images, matrices, offsets, fills, out_shape, mode, reject, trim, kappa, iters, weights, empty, counts, out,
+                          interp=None):
+        """the body of ``stack_clip_batch``"""
+        interp = _lib.interp_code(interp, mode, self.RGB)
         if self.RGB:
             raise RuntimeError("stack_clip_batch reduces float32 frames; an RGB plan has no stack reduction")
         code, n_low, n_high, kl, kh, iters, w = self._clip_args(reject, trim, kappa, iters, weights)
@@ -475,10 +500,10 @@ class BatchPlan(SiftPlan):
             pptr, cptr, kptr = plane.ctypes.data, (cover.ctypes.data if counts else None), (kept.ctypes.data if counts else None)
         ms = C.c_double(0)
         with self._sem:
-            _lib.check(_lib.lib().siftmi_batch_stack_clip(self._handle, ptrs, n, is_dev, pptr, cptr, kptr, int(out == "device"), ow, oh,
-                                                          maps.ctypes.data, f.ctypes.data, None if w is None else w.ctypes.data, int(mode),
-                                                          code, n_low, n_high, C.c_float(kl), C.c_float(kh), iters, C.c_float(empty),
-                                                          C.byref(ms)))
+            _lib.check(_lib.lib().siftmi_batch_stack_clip_ex(self._handle, ptrs, n, is_dev, pptr, cptr, kptr, int(out == "device"), ow, oh,
+                                                             maps.ctypes.data, f.ctypes.data, None if w is None else w.ctypes.data, int(mode),
+                                                             interp, code, n_low, n_high, C.c_float(kl), C.c_float(kh), iters,
+                                                             C.c_float(empty), C.byref(ms)))
         self.last_stack_ms = ms.value
         del keep
         return (plane, cover, kept) if counts else plane

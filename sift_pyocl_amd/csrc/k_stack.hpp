@@ -52,18 +52,28 @@
 // stack_reduce_kernel<false>, <true> and stack_median_kernel (67 SGPRs each); 0 bytes of scratch, no spill and 8 waves per
 // SIMD by registers for all three; no static LDS.
 //
+// Cubic instances: stack_reduce_cubic_kernel<MEAN> and stack_median_cubic_kernel sample with
+// k_warp_cubic.hpp's cubic_taps / cubic_value instead of transform_taps / transform_value, SIFT_STACK_DEPTH_CUBIC = 2 frames at a time
+// (16 taps a frame); live frames, the order of every sum, the LDS column and the launch (shape and dynamic LDS) are the same.  The
+// body of each kernel is ONE text that the legacy kernel and its cubic twin include (k_stack_reduce_body.hpp,
+// k_stack_median_body.hpp; why an include and not a template is said there): the legacy kernels compile to the code they had.
+// Resources of the cubic instances: reduce 70 VGPRs (7 waves per SIMD), median 74 (6 waves); no scratch, no static LDS.
+//
 // Bounds: x < OW and y < OH by the launch shape and the first test; reads stay inside image_s (W x H, the batch's shape) by
 // transform_taps, which forms no index unless the point is inside; rows s < S of the table only; an LDS slot is an insertion
 // point j <= min(c, K - 1) or a rank <= c >> 1 <= K - 1 read only when c >= 1, so the word index 256 * j + t is < K * 256, which
 // is what the launch asks for, and K <= S for every S >= 1: the index is < S * 256; output offsets y * OW + x are formed in size_t.
 #pragma once
-#include "k_align_batch.hpp"
+#include "k_warp_cubic.hpp"
 
 namespace siftk {
 
 #define SIFT_STACK_MEDIAN_MAX 64
 #ifndef SIFT_STACK_DEPTH
 #define SIFT_STACK_DEPTH 4                 // frames whose taps are loaded before their values are formed
+#endif
+#ifndef SIFT_STACK_DEPTH_CUBIC
+#define SIFT_STACK_DEPTH_CUBIC 2           // the same for the cubic instances: 16 taps a frame instead of 4 (1 and 4 measured slower)
 #endif
 
 __device__ __forceinline__ uint32_t stack_key(float v) {
@@ -86,28 +96,25 @@ __device__ __forceinline__ void stack_add(float &acc, int &c, float v, bool live
 template <bool MEAN>
 __global__ __launch_bounds__(256) void stack_reduce_kernel(const WarpFrame *__restrict__ frames, int S, float *__restrict__ out,
                                                            int32_t *__restrict__ coverage, int W, int H, int OW, int OH, float empty) {
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= OW || y >= OH) return;
-    float acc = 0.0f;
-    int c = 0, s = 0;
-    for (; s + SIFT_STACK_DEPTH <= S; s += SIFT_STACK_DEPTH) {
-        WarpFrame f[SIFT_STACK_DEPTH];
-        WarpTaps t[SIFT_STACK_DEPTH];
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) f[k] = frames[s + k];
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) t[k] = transform_taps(static_cast<const float *>(f[k].image), f[k].a, W, H, x, y);
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) stack_add(acc, c, transform_value(t[k], f[k].a, W, H), transform_live(t[k], W, H));
-    }
-    for (; s < S; s++) {
-        const WarpFrame f = frames[s];
-        const WarpTaps t = transform_taps(static_cast<const float *>(f.image), f.a, W, H, x, y);
-        stack_add(acc, c, transform_value(t, f.a, W, H), transform_live(t, W, H));
-    }
-    const size_t o = (size_t)y * OW + x;
-    out[o] = c ? (MEAN ? acc / (float)c : acc) : empty;
-    if (coverage) coverage[o] = c;
+#define STACK_BODY_TAPS_T WarpTaps
+#define STACK_BODY_TAPS transform_taps
+#define STACK_BODY_DEPTH SIFT_STACK_DEPTH
+#include "k_stack_reduce_body.hpp"
+#undef STACK_BODY_TAPS_T
+#undef STACK_BODY_TAPS
+#undef STACK_BODY_DEPTH
+}
+
+template <bool MEAN>
+__global__ __launch_bounds__(256) void stack_reduce_cubic_kernel(const WarpFrame *__restrict__ frames, int S, float *__restrict__ out,
+                                                                 int32_t *__restrict__ coverage, int W, int H, int OW, int OH, float empty) {
+#define STACK_BODY_TAPS_T CubicTaps
+#define STACK_BODY_TAPS cubic_taps
+#define STACK_BODY_DEPTH SIFT_STACK_DEPTH_CUBIC
+#include "k_stack_reduce_body.hpp"
+#undef STACK_BODY_TAPS_T
+#undef STACK_BODY_TAPS
+#undef STACK_BODY_DEPTH
 }
 
 // one more live key into the sorted column of this thread (col points at its slot 0; slots are 256 words apart)
@@ -128,35 +135,24 @@ __device__ __forceinline__ void stack_insert(uint32_t *col, int K, int &c, uint3
 
 __global__ __launch_bounds__(256) void stack_median_kernel(const WarpFrame *__restrict__ frames, int S, float *__restrict__ out,
                                                            int32_t *__restrict__ coverage, int W, int H, int OW, int OH, float empty) {
-    extern __shared__ uint32_t stack_keys[];       // [K][256]
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= OW || y >= OH) return;
-    uint32_t *col = stack_keys + threadIdx.y * 64 + threadIdx.x;
-    const int K = stack_median_slots(S);
-    int c = 0, s = 0;
-    for (; s + SIFT_STACK_DEPTH <= S; s += SIFT_STACK_DEPTH) {
-        WarpFrame f[SIFT_STACK_DEPTH];
-        WarpTaps t[SIFT_STACK_DEPTH];
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) f[k] = frames[s + k];
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) t[k] = transform_taps(static_cast<const float *>(f[k].image), f[k].a, W, H, x, y);
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) stack_insert(col, K, c, stack_key(transform_value(t[k], f[k].a, W, H)), transform_live(t[k], W, H));
-    }
-    for (; s < S; s++) {
-        const WarpFrame f = frames[s];
-        const WarpTaps t = transform_taps(static_cast<const float *>(f.image), f.a, W, H, x, y);
-        stack_insert(col, K, c, stack_key(transform_value(t, f.a, W, H)), transform_live(t, W, H));
-    }
-    float r = empty;
-    if (c) {
-        const float lo = stack_unkey(col[256 * ((c - 1) >> 1)]);
-        r = (c & 1) ? lo : (lo + stack_unkey(col[256 * (c >> 1)])) * 0.5f;
-    }
-    const size_t o = (size_t)y * OW + x;
-    out[o] = r;
-    if (coverage) coverage[o] = c;
+#define STACK_BODY_TAPS_T WarpTaps
+#define STACK_BODY_TAPS transform_taps
+#define STACK_BODY_DEPTH SIFT_STACK_DEPTH
+#include "k_stack_median_body.hpp"
+#undef STACK_BODY_TAPS_T
+#undef STACK_BODY_TAPS
+#undef STACK_BODY_DEPTH
+}
+
+__global__ __launch_bounds__(256) void stack_median_cubic_kernel(const WarpFrame *__restrict__ frames, int S, float *__restrict__ out,
+                                                                 int32_t *__restrict__ coverage, int W, int H, int OW, int OH, float empty) {
+#define STACK_BODY_TAPS_T CubicTaps
+#define STACK_BODY_TAPS cubic_taps
+#define STACK_BODY_DEPTH SIFT_STACK_DEPTH_CUBIC
+#include "k_stack_median_body.hpp"
+#undef STACK_BODY_TAPS_T
+#undef STACK_BODY_TAPS
+#undef STACK_BODY_DEPTH
 }
 
 }  // namespace siftk

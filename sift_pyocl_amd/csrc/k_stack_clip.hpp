@@ -51,6 +51,10 @@
 // <SIGMA> 60 (73 SGPRs each); 0 bytes of scratch, no spill and 8 waves per SIMD by registers for both; no static LDS.  What
 // limits the waves is the dynamic LDS: S * 256 bytes per wave, all 8 per SIMD up to S = 20, 2 at S = 64.
 //
+// Cubic instances: stack_clip_cubic_kernel<REJECT> is the same body (k_stack_clip_body.hpp, included
+// by both kernels) sampling with k_warp_cubic.hpp's cubic_taps / cubic_value, SIFT_STACK_DEPTH_CUBIC frames at a time; the same launch
+// and the same dynamic LDS.  <TRIM> 72 VGPRs (7 waves per SIMD by registers), <SIGMA> 76 (6 waves); no scratch, no static LDS.
+//
 // Bounds: x < OW and y < OH by the launch shape and the first test; image reads stay inside image_s by transform_taps; rows s < S
 // of the table only; an LDS word is s * 256 + t with s < S and t < 256, below the S * 256 words the launch asks for; weights w[s]
 // with s < S <= 64 = the array's length (the library refuses S > 64 before the launch); a selection scan runs only while
@@ -75,109 +79,26 @@ template <int REJECT>
 __global__ __launch_bounds__(256) void stack_clip_kernel(const WarpFrame *__restrict__ frames, int S, const StackClipArgs p,
                                                          float *__restrict__ out, int32_t *__restrict__ coverage,
                                                          int32_t *__restrict__ kept, int W, int H, int OW, int OH, float empty) {
-    extern __shared__ float stack_vals[];          // [S][256]
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= OW || y >= OH) return;
-    float *col = stack_vals + threadIdx.y * 64 + threadIdx.x;
-    uint64_t K = 0;
-    float acc = 0.0f;                              // osum(v) over the live frames: the first SIGMA pass's
-    int c = 0, s = 0;
-    for (; s + SIFT_STACK_DEPTH <= S; s += SIFT_STACK_DEPTH) {
-        WarpFrame f[SIFT_STACK_DEPTH];
-        WarpTaps t[SIFT_STACK_DEPTH];
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) f[k] = frames[s + k];
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) t[k] = transform_taps(static_cast<const float *>(f[k].image), f[k].a, W, H, x, y);
-#pragma unroll
-        for (int k = 0; k < SIFT_STACK_DEPTH; k++) {
-            const float v = transform_value(t[k], f[k].a, W, H);
-            const bool live = transform_live(t[k], W, H);
-            col[256 * (s + k)] = v;
-            K |= (uint64_t)live << (s + k);
-            stack_add(acc, c, v, live);
-        }
-    }
-    for (; s < S; s++) {
-        const WarpFrame f = frames[s];
-        const WarpTaps t = transform_taps(static_cast<const float *>(f.image), f.a, W, H, x, y);
-        const float v = transform_value(t, f.a, W, H);
-        const bool live = transform_live(t, W, H);
-        col[256 * s] = v;
-        K |= (uint64_t)live << s;
-        stack_add(acc, c, v, live);
-    }
-    int n = c;
-    if (REJECT == SIFT_STACK_TRIM) {
-        if (c > 1) {
-            const int h = min(p.n_high, c - 1), l = min(p.n_low, c - 1 - h);
-            for (int i = 0; i < h; i++) {          // the largest (key, s) of K: among equal keys the last frame
-                uint32_t best_key = 0;
-                int best = 0;
-                for (int j = 0; j < S; j++) {
-                    const uint32_t k = stack_key(col[256 * j]);
-                    if (((K >> j) & 1) && k >= best_key) { best_key = k; best = j; }
-                }
-                K &= ~((uint64_t)1 << best);
-            }
-            for (int i = 0; i < l; i++) {          // the smallest (key, s) of K: among equal keys the first frame
-                uint32_t best_key = 0xffffffffu;
-                int best = -1;
-                for (int j = 0; j < S; j++) {
-                    const uint32_t k = stack_key(col[256 * j]);
-                    if (((K >> j) & 1) && (best < 0 || k < best_key)) { best_key = k; best = j; }
-                }
-                K &= ~((uint64_t)1 << best);
-            }
-            n = c - h - l;
-        }
-    } else {
-        const float kl2 = p.kappa_low * p.kappa_low, kh2 = p.kappa_high * p.kappa_high;
-        float sum = acc;
-        for (int it = 0; it < p.iters && n >= 3; it++) {
-            const float m = sum / (float)n;
-            float q = 0.0f;
-            bool first = true;
-            for (int j = 0; j < S; j++) {
-                const float d = col[256 * j] - m;
-                const float dd = d * d;
-                if ((K >> j) & 1) { q = first ? dd : q + dd; first = false; }
-            }
-            const float var = q / (float)n;
-            const float tl = kl2 * var, th = kh2 * var;
-            uint64_t gone = 0;
-            float rest = 0.0f;                     // osum(v) over what stays: the next pass's
-            int stay = 0;
-            for (int j = 0; j < S; j++) {
-                const float v = col[256 * j];
-                const float d = v - m;
-                const float dd = d * d;
-                const bool in = (K >> j) & 1;
-                const bool off = in && ((d < 0.0f && dd > tl) || (d > 0.0f && dd > th));
-                gone |= (uint64_t)off << j;
-                stack_add(rest, stay, v, in && !off);
-            }
-            if (gone == 0 || stay == 0) break;     // nothing to remove; or everything, which removes none
-            K &= ~gone;
-            n = stay;
-            sum = rest;
-        }
-    }
-    float r = empty;
-    if (c) {
-        float num = 0.0f, den = 0.0f;
-        bool first = true;
-        for (int j = 0; j < S; j++) {
-            const float w = p.w[j];
-            const float wv = w * col[256 * j];
-            if ((K >> j) & 1) { num = first ? wv : num + wv; den = first ? w : den + w; first = false; }
-        }
-        r = num / den;
-    }
-    const size_t o = (size_t)y * OW + x;
-    out[o] = r;
-    if (coverage) coverage[o] = c;
-    if (kept) kept[o] = c ? n : 0;
+#define STACK_BODY_TAPS_T WarpTaps
+#define STACK_BODY_TAPS transform_taps
+#define STACK_BODY_DEPTH SIFT_STACK_DEPTH
+#include "k_stack_clip_body.hpp"
+#undef STACK_BODY_TAPS_T
+#undef STACK_BODY_TAPS
+#undef STACK_BODY_DEPTH
+}
+
+template <int REJECT>
+__global__ __launch_bounds__(256) void stack_clip_cubic_kernel(const WarpFrame *__restrict__ frames, int S, const StackClipArgs p,
+                                                               float *__restrict__ out, int32_t *__restrict__ coverage,
+                                                               int32_t *__restrict__ kept, int W, int H, int OW, int OH, float empty) {
+#define STACK_BODY_TAPS_T CubicTaps
+#define STACK_BODY_TAPS cubic_taps
+#define STACK_BODY_DEPTH SIFT_STACK_DEPTH_CUBIC
+#include "k_stack_clip_body.hpp"
+#undef STACK_BODY_TAPS_T
+#undef STACK_BODY_TAPS
+#undef STACK_BODY_DEPTH
 }
 
 }  // namespace siftk

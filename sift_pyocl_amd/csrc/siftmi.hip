@@ -23,6 +23,7 @@
 #include "k_descriptor.hpp"
 #include "k_align.hpp"
 #include "k_align_batch.hpp"
+#include "k_warp_cubic.hpp"
 #include "k_stack.hpp"
 #include "k_stack_clip.hpp"
 #include "k_pyramid.hpp"
@@ -2103,10 +2104,18 @@ int warp_end(siftmi_batch *b, const WarpIo &io, void *host0, size_t bytes0, void
 
 // The one launch site of the stack reduction (k_stack.hpp): S frames of W x H from the device table to one OH x OW plane and,
 // unless null, its coverage.  S == 0 (sum or mean) fills the plane with `empty` and the coverage with 0.
-void launch_stack(hipStream_t st, int reduce, const WarpFrame *frames, int S, float *out, int32_t *coverage, int W, int H, int OW, int OH,
-                  float empty) {
+void launch_stack(hipStream_t st, int reduce, int interp, const WarpFrame *frames, int S, float *out, int32_t *coverage, int W, int H, int OW,
+                  int OH, float empty) {
     const dim3 grid((unsigned)((OW + 63) / 64), (unsigned)((OH + 3) / 4)), block(64, 4);
-    if (reduce == SIFTMI_STACK_MEDIAN)
+    if (interp == SIFTMI_INTERP_CUBIC) {           // the cubic instances: the same launch shapes and the same dynamic LDS
+        if (reduce == SIFTMI_STACK_MEDIAN)
+            hipLaunchKernelGGL(stack_median_cubic_kernel, grid, block, (size_t)stack_median_slots(S) * 256 * sizeof(uint32_t), st, frames, S, out,
+                               coverage, W, H, OW, OH, empty);
+        else if (reduce == SIFTMI_STACK_MEAN)
+            hipLaunchKernelGGL(stack_reduce_cubic_kernel<true>, grid, block, 0, st, frames, S, out, coverage, W, H, OW, OH, empty);
+        else
+            hipLaunchKernelGGL(stack_reduce_cubic_kernel<false>, grid, block, 0, st, frames, S, out, coverage, W, H, OW, OH, empty);
+    } else if (reduce == SIFTMI_STACK_MEDIAN)
         hipLaunchKernelGGL(stack_median_kernel, grid, block, (size_t)stack_median_slots(S) * 256 * sizeof(uint32_t), st, frames, S, out, coverage, W, H,
                            OW, OH, empty);
     else if (reduce == SIFTMI_STACK_MEAN)
@@ -2117,22 +2126,45 @@ void launch_stack(hipStream_t st, int reduce, const WarpFrame *frames, int S, fl
 
 // The one launch site of the clipped stack reduction (k_stack_clip.hpp): S <= 64 frames to one OH x OW plane and, unless null, its
 // coverage and kept counts.  Dynamic LDS is the S x 256 samples of a block.  S == 0 fills the plane with `empty` and both counts with 0.
-void launch_stack_clip(hipStream_t st, int reject, const WarpFrame *frames, int S, const StackClipArgs &p, float *out, int32_t *coverage,
-                       int32_t *kept, int W, int H, int OW, int OH, float empty) {
+void launch_stack_clip(hipStream_t st, int reject, int interp, const WarpFrame *frames, int S, const StackClipArgs &p, float *out,
+                       int32_t *coverage, int32_t *kept, int W, int H, int OW, int OH, float empty) {
     const dim3 grid((unsigned)((OW + 63) / 64), (unsigned)((OH + 3) / 4)), block(64, 4);
     const size_t lds = (size_t)S * 256 * sizeof(float);
-    if (reject == SIFTMI_STACK_TRIM)
+    if (interp == SIFTMI_INTERP_CUBIC) {
+        if (reject == SIFTMI_STACK_TRIM)
+            hipLaunchKernelGGL(stack_clip_cubic_kernel<SIFT_STACK_TRIM>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
+        else
+            hipLaunchKernelGGL(stack_clip_cubic_kernel<SIFT_STACK_SIGMA>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
+    } else if (reject == SIFTMI_STACK_TRIM)
         hipLaunchKernelGGL(stack_clip_kernel<SIFT_STACK_TRIM>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
     else
         hipLaunchKernelGGL(stack_clip_kernel<SIFT_STACK_SIGMA>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
 }
+
+// What every _ex entry refuses about its sampler before anything else is looked at: an unknown `interp`, and the cubic sampler with
+// a `mode` other than 1 (reserved) or for RGB8 frames.  SIFTMI_OK otherwise.
+int check_interp(int32_t interp, int32_t mode, bool rgb) {
+    static_assert(SIFTMI_INTERP_MODE == SIFT_INTERP_MODE && SIFTMI_INTERP_CUBIC == SIFT_INTERP_CUBIC, "siftmi.h and k_warp_cubic.hpp disagree");
+    if (interp != SIFTMI_INTERP_MODE && interp != SIFTMI_INTERP_CUBIC) return fail(SIFTMI_EINVAL, "interp must be 0 (what mode says) or 1 (cubic), got %d", interp);
+    if (interp == SIFTMI_INTERP_CUBIC && mode != 1) return fail(SIFTMI_EINVAL, "the cubic sampler takes mode 1 only (other values are reserved), got %d", mode);
+    if (interp == SIFTMI_INTERP_CUBIC && rgb) return fail(SIFTMI_EINVAL, "the cubic sampler takes float32 frames only");
+    return SIFTMI_OK;
+}
 }  // namespace
 
-// The warp of siftmi_plan_transform for n frames in one launch (k_align_batch.hpp).
+// The warp of siftmi_plan_transform for n frames in one launch (k_align_batch.hpp; cubic: k_warp_cubic.hpp).
 int siftmi_batch_transform(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device,
                            int32_t channels, void *out, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps,
                            const float *fills, int32_t mode, double *kernel_ms) {
+    return siftmi_batch_transform_ex(b, images, n_images, images_are_device, channels, out, out_is_device, OW, OH, maps, fills, mode,
+                                     SIFTMI_INTERP_MODE, kernel_ms);
+}
+
+int siftmi_batch_transform_ex(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device,
+                              int32_t channels, void *out, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps,
+                              const float *fills, int32_t mode, int32_t interp, double *kernel_ms) {
     if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (int rc = check_interp(interp, mode, channels == 3 || (!b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8))) return rc;
     if (n_images < 0) return fail(SIFTMI_EINVAL, "negative image count");
     if (n_images > 65535) return fail(SIFTMI_EINVAL, "%d frames: more than 65535 (one grid plane per frame)", n_images);
     if (channels != 1 && channels != 3) return fail(SIFTMI_EINVAL, "channels must be 1 (float32) or 3 (RGB8), got %d", channels);
@@ -2152,7 +2184,9 @@ int siftmi_batch_transform(siftmi_batch *b, const void *const *images, int32_t n
     const int xcols = channels == 1 ? 64 : 256;   // RGB: 4 pixels per thread
     const dim3 grid((unsigned)((OW + xcols - 1) / xcols), (unsigned)((OH + 3) / 4), (unsigned)n_images), block(64, 4);
     hipEventRecord(b->ev_wa, io.stream);
-    if (channels == 1)
+    if (interp == SIFTMI_INTERP_CUBIC)
+        hipLaunchKernelGGL(transform_cubic_batch_kernel, grid, block, 0, io.stream, (const WarpFrame *)b->warp_tab, (float *)io.dst, io.W, io.H, OW, OH);
+    else if (channels == 1)
         hipLaunchKernelGGL(transform_batch_kernel, grid, block, 0, io.stream, (const WarpFrame *)b->warp_tab, (float *)io.dst, io.W, io.H, OW, OH);
     else
         hipLaunchKernelGGL(transform_rgb_batch_kernel, grid, block, 0, io.stream, (const WarpFrame *)b->warp_tab, (uint8_t *)io.dst, io.W, io.H, OW, OH);
@@ -2165,7 +2199,15 @@ int siftmi_batch_transform(siftmi_batch *b, const void *const *images, int32_t n
 int siftmi_batch_stack(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, float *out,
                        int32_t *coverage, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps, const float *fills,
                        int32_t mode, int32_t reduce, float empty, double *kernel_ms) {
+    return siftmi_batch_stack_ex(b, images, n_images, images_are_device, out, coverage, out_is_device, OW, OH, maps, fills, mode,
+                                 SIFTMI_INTERP_MODE, reduce, empty, kernel_ms);
+}
+
+int siftmi_batch_stack_ex(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, float *out,
+                          int32_t *coverage, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps, const float *fills,
+                          int32_t mode, int32_t interp, int32_t reduce, float empty, double *kernel_ms) {
     if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (int rc = check_interp(interp, mode, !b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8)) return rc;
     if (n_images < 0) return fail(SIFTMI_EINVAL, "negative image count");
     if (n_images > 65535) return fail(SIFTMI_EINVAL, "%d frames: more than 65535", n_images);
     if (reduce != SIFTMI_STACK_SUM && reduce != SIFTMI_STACK_MEAN && reduce != SIFTMI_STACK_MEDIAN)
@@ -2189,7 +2231,7 @@ int siftmi_batch_stack(siftmi_batch *b, const void *const *images, int32_t n_ima
     // a host result: the plane, then the coverage, in the batch's staging
     int32_t *cov = out_is_device ? coverage : (coverage ? reinterpret_cast<int32_t *>((uint8_t *)io.dst + plane) : nullptr);
     hipEventRecord(b->ev_wa, io.stream);
-    launch_stack(io.stream, n_images ? reduce : SIFTMI_STACK_SUM, (const WarpFrame *)b->warp_tab, n_images, (float *)io.dst, cov, io.W, io.H, OW, OH, empty);
+    launch_stack(io.stream, n_images ? reduce : SIFTMI_STACK_SUM, interp, (const WarpFrame *)b->warp_tab, n_images, (float *)io.dst, cov, io.W, io.H, OW, OH, empty);
     hipEventRecord(b->ev_wb, io.stream);
     return warp_end(b, io, out_is_device ? nullptr : out, plane, coverage, plane, kernel_ms);
 }
@@ -2200,7 +2242,16 @@ int siftmi_batch_stack_clip(siftmi_batch *b, const void *const *images, int32_t 
                             int32_t *coverage, int32_t *kept, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps,
                             const float *fills, const float *weights, int32_t mode, int32_t reject, int32_t n_low, int32_t n_high,
                             float kappa_low, float kappa_high, int32_t iters, float empty, double *kernel_ms) {
+    return siftmi_batch_stack_clip_ex(b, images, n_images, images_are_device, out, coverage, kept, out_is_device, OW, OH, maps, fills, weights,
+                                      mode, SIFTMI_INTERP_MODE, reject, n_low, n_high, kappa_low, kappa_high, iters, empty, kernel_ms);
+}
+
+int siftmi_batch_stack_clip_ex(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, float *out,
+                               int32_t *coverage, int32_t *kept, int32_t out_is_device, int32_t OW, int32_t OH, const float *maps,
+                               const float *fills, const float *weights, int32_t mode, int32_t interp, int32_t reject, int32_t n_low,
+                               int32_t n_high, float kappa_low, float kappa_high, int32_t iters, float empty, double *kernel_ms) {
     if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (int rc = check_interp(interp, mode, !b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8)) return rc;
     if (n_images < 0) return fail(SIFTMI_EINVAL, "negative image count");
     static_assert(SIFTMI_STACK_CLIP_MAX == SIFT_STACK_CLIP_MAX && SIFTMI_STACK_TRIM == SIFT_STACK_TRIM && SIFTMI_STACK_SIGMA == SIFT_STACK_SIGMA,
                   "siftmi.h and k_stack_clip.hpp disagree");
@@ -2238,7 +2289,7 @@ int siftmi_batch_stack_clip(siftmi_batch *b, const void *const *images, int32_t 
         kep = kept ? reinterpret_cast<int32_t *>((uint8_t *)io.dst + 2 * plane) : nullptr;
     }
     hipEventRecord(b->ev_wa, io.stream);
-    launch_stack_clip(io.stream, reject, (const WarpFrame *)b->warp_tab, n_images, p, (float *)io.dst, cov, kep, io.W, io.H, OW, OH, empty);
+    launch_stack_clip(io.stream, reject, interp, (const WarpFrame *)b->warp_tab, n_images, p, (float *)io.dst, cov, kep, io.W, io.H, OW, OH, empty);
     hipEventRecord(b->ev_wb, io.stream);
     return warp_end(b, io, out_is_device ? nullptr : out, plane, coverage, plane, kernel_ms, kept, plane);
 }
@@ -2254,7 +2305,15 @@ int siftmi_plan_records_device(const siftmi_plan *p, const siftmi_keypoint **rec
 int siftmi_plan_transform(siftmi_plan *p, const void *image, int32_t image_is_device, int32_t channels, void *out,
                           int32_t out_is_device, int32_t OW, int32_t OH, const float *matrix, const float *offset, float fill,
                           int32_t mode, double *kernel_ms) {
+    return siftmi_plan_transform_ex(p, image, image_is_device, channels, out, out_is_device, OW, OH, matrix, offset, fill, mode,
+                                    SIFTMI_INTERP_MODE, kernel_ms);
+}
+
+int siftmi_plan_transform_ex(siftmi_plan *p, const void *image, int32_t image_is_device, int32_t channels, void *out,
+                             int32_t out_is_device, int32_t OW, int32_t OH, const float *matrix, const float *offset, float fill,
+                             int32_t mode, int32_t interp, double *kernel_ms) {
     if (!p || !out || !matrix || !offset) return fail(SIFTMI_EINVAL, "null argument");
+    if (int rc = check_interp(interp, mode, channels == 3)) return rc;
     if (channels != 1 && channels != 3) return fail(SIFTMI_EINVAL, "channels must be 1 (float32) or 3 (RGB8), got %d", channels);
     if (OW < 0 || OH < 0) return fail(SIFTMI_EINVAL, "negative output shape");
     HIPCHK(hipSetDevice(p->device));
@@ -2296,7 +2355,9 @@ int siftmi_plan_transform(siftmi_plan *p, const void *image, int32_t image_is_de
         const int xcols = channels == 1 ? 64 : 256;   // RGB: 4 pixels per thread
         const dim3 grid((unsigned)((OW + xcols - 1) / xcols), (unsigned)((OH + 3) / 4)), block(64, 4);
         hipEventRecord(p->ev_wa, p->stream);
-        if (channels == 1)
+        if (interp == SIFTMI_INTERP_CUBIC)
+            hipLaunchKernelGGL(transform_cubic_kernel, grid, block, 0, p->stream, (const float *)src, (float *)dst, a, p->W, p->H, OW, OH);
+        else if (channels == 1)
             hipLaunchKernelGGL(transform_kernel, grid, block, 0, p->stream, (const float *)src, (float *)dst, a, p->W, p->H, OW, OH);
         else
             hipLaunchKernelGGL(transform_rgb_kernel, grid, block, 0, p->stream, (const uint8_t *)src, (uint8_t *)dst, a, p->W, p->H, OW, OH);
