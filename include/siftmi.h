@@ -149,15 +149,18 @@ int siftmi_plan_records_device(const siftmi_plan *plan, const siftmi_keypoint **
 /* What the last finished siftmi_plan_keypoints left behind besides its records (read-only test hooks: the pyramid of every
  * producer -- marching, tile and generic blurs, the fused hand-off, octave_tail_kernel -- compared plane by plane at plan level).
  * The reference keeps the same planes in buffers["scale_<octave>_<scale>"] (plan.py:276-285) and reads its keypoint counter back
- * after every local_maxmin (plan.py:642).  Neither call launches anything; both are valid until the next call on the plan.
+ * after every local_maxmin (plan.py:642).  Neither call launches anything (but see below); both are valid until the next call on the plan.
  * siftmi_plan_planes       copies the six blur planes of `octave` (scale 0 first, row pitch W) to the host buffer `out` of
  *                          `capacity` floats, 6 * W * H of them, and returns the octave's W and H (either may be null).  It waits
- *                          for the plan's streams only.  Octave planes are never rewritten within a call.
+ *                          for the plan's streams only.  Octave planes are never rewritten within a call.  An octave whose last
+ *                          run wrote plane 5 only around its scale-3 candidates (siftmi_plan_set_lazy_top) gets the blur launch it
+ *                          went without first: the planes returned are whole either way.
  * siftmi_plan_last_counts  host integers of the complete read-back of the counters that the wait selected:
  *   tail_first     first octave that octave_tail_kernel took in the run that produced the result, n_octaves of the plan when
  *                  there was no tail launch (also after a tail time-out: the result then comes from the re-run)
  *   candidates     [n_octaves] entries the octave's detection appended to its candidate list (a split octave 0's second slot
  *                  folded in).  The fused detect-and-refine launch keeps no candidate list: its octaves read 0 here.
+ *                  (Under siftmi_plan_set_lazy_top the provisional scale-3 entries that were rejected do not count.)
  *   c_scale        [n_octaves][3] candidates of the octave per detection scale 1, 2, 3, as the refinement read them
  *   n_octaves      octaves the two arrays have room for (>= the plan's)
  * siftmi_plan_tail_candidates  copies the candidate list octave_tail_kernel kept for `octave` -- min(candidates[octave], 3 * 4096)
@@ -170,6 +173,21 @@ int siftmi_plan_planes(siftmi_plan *plan, int32_t octave, float *out, int64_t ca
 int siftmi_plan_last_counts(const siftmi_plan *plan, int32_t *tail_first, int32_t *candidates, int32_t *c_scale,
                             int32_t n_octaves);
 int siftmi_plan_tail_candidates(const siftmi_plan *plan, int32_t octave, float *out, int64_t capacity, int64_t *count);
+/* The top blur plane (plane 5 of an octave) only around scale-3 candidates.  Plane 5 is read at few places: by the extrema pass as
+ * the outer layer of scale 3's 27-neighbour test, by the refinement of a scale-3 candidate.  An octave that runs lazily skips
+ * the blur launch that writes plane 5, tests scale 3 against 18 neighbours, evaluates plane 5 on a 13 x 13 patch around every
+ * provisional candidate (top_patch_kernel) and finishes the test there.  Only octaves whose detection keeps a candidate
+ * list run lazily (not the fused detect-and-refine form, not the tail launch, not under the full profile).  Records never
+ * depend on it.
+ *   mode     0 never, 1 always, 2 (the default) per octave when the previous image of the plan left fewer than one scale-3
+ *            candidate per `density` pixels in that octave; a plan's first image is eager
+ *   density  pixels per scale-3 candidate of the automatic rule (default 6000); <= 0 keeps the plan's value
+ *   blocks   one-wave workgroups of top_patch_kernel (default 8192, at most 65535); <= 0 keeps the plan's value */
+int siftmi_plan_set_lazy_top(siftmi_plan *plan, int32_t mode, int32_t density, int32_t blocks);
+/* lazy[o] = 1 for every octave o of the last finished call that ran the lazy detection chain (siftmi_plan_set_lazy_top: no full plane 5,
+ * provisional scale-3 candidates, top_patch_kernel), else 0; n_octaves: room in `lazy` (>= the plan's).  Read-only test hook
+ * for the automatic rule; SIFTMI_EINVAL as siftmi_plan_last_counts. */
+int siftmi_plan_lazy_octaves(const siftmi_plan *plan, int32_t *lazy, int32_t n_octaves);
 /* Affine warp with bilinear interpolation of an image of the plan's shape -- the `transform` / `transform_RGB`
  * kernels (openCL/transform.cl:22, :116) as LinearAlign.align launches them (sift-src/alignment.py:325-348).
  *   out[y][x] = bilinear(image, (ty, tx)),  ty = matrix[0]*y + matrix[1]*x + offset[0],
@@ -732,6 +750,22 @@ int siftmi_stage_detect_ex(int32_t device_id, const float *blurs, int32_t W, int
                            const siftmi_params *params, int32_t form, int32_t rows, int32_t xcd_map, int32_t y_lo, int32_t y_hi,
                            int64_t cand_capacity, int64_t kp_capacity, float *cand, float *kp, int32_t *kp_aux,
                            int32_t *counters);
+/* The lazy detection chain of a plan (siftmi_plan_set_lazy_top) on five planes: the extrema launch that does not read plane 5 (scale 3
+ * against 18 neighbours: provisional candidates), top_patch_kernel (plane 5 from plane 4 with `top_taps` on the 13 x 13 patch
+ * around every provisional candidate, clipped to the plane; a candidate whose DoG4 3 x 3 holds a sample beyond it becomes a
+ * hole, four times -1.0f), then the refinement launch.
+ *   blurs5         (5, H, W) planes 0..4
+ *   top_taps       n_taps (1..64) taps of the blur from plane 4 to plane 5
+ *   rows .. kp_aux as siftmi_stage_detect_ex (form 0); `cand` comes back with the holes in it
+ *   counters       as siftmi_stage_detect_ex; counters[0] counts the provisional entries too
+ *   plane5         (H, W) the plane-5 buffer of the run: every float was SIFTMI_STAGE_TOP_FILL (a quiet NaN with a payload)
+ *                  before the launches, so the samples no patch covers come back as the fill, and a refinement read outside
+ *                  the patches would have turned a peak into NaN. */
+#define SIFTMI_STAGE_TOP_FILL 0x7fc5a5a5u
+int siftmi_stage_detect_lazy(int32_t device_id, const float *blurs5, const float *top_taps, int32_t n_taps, int32_t W, int32_t H,
+                             int32_t octsize, const siftmi_params *params, int32_t rows, int32_t xcd_map, int32_t y_lo, int32_t y_hi,
+                             int64_t cand_capacity, int64_t kp_capacity, float *cand, float *kp, int32_t *kp_aux,
+                             int32_t *counters, float *plane5);
 /* `compact` (openCL/algebra.cl:57-84, host side plan.py:758-795): rows [start, end) of kps (n,4) whose row field is not
  * -1 are moved up to follow the first `start` rows; out receives *n_out rows (start + survivors), survivors unordered */
 int siftmi_stage_compact(int32_t device_id, const float *kps, int64_t n, int64_t start, int64_t end, float *out, int64_t *n_out);

@@ -115,7 +115,10 @@ __device__ __forceinline__ void ext_edge_filter(const BlurPlanes &b, int W, floa
 // caller's to flush.
 // REFINE: the survivors of the edge test are refined and appended to the keypoint list right here, one parked entry per
 // lane (no candidate list, no refinement launch); nothing is left parked on return.
-template <int BUF, bool REFINE = false>
+// LAZY: plane 5 is not read.  The march loads planes 0-4 and forms d[0..3]; scale 3's rolling max / min cover d[2], d[3]
+// only (the 18-neighbour test), scales 1 and 2 are unchanged.  The scale-3 entries this leaves in the candidate list are
+// provisional: top_patch_kernel (k_top_patch.hpp) evaluates plane 5 around each of them and applies the outer layer.
+template <int BUF, bool REFINE = false, bool LAZY = false>
 __device__ __forceinline__ void extrema_strip(const BlurPlanes &b, int W, int H, int border, int rows, bool active, int sx, int sy,
                                               double contrast, float edth, float4 *__restrict__ cand, int *__restrict__ counter,
                                               int capacity, ExtWaveLdsT<BUF> &L, int &pending, const RefineArgs *ra = nullptr,
@@ -158,26 +161,28 @@ __device__ __forceinline__ void extrema_strip(const BlurPlanes &b, int W, int H,
 
     const unsigned pitch = (unsigned)W * 4u;
     unsigned off = ((unsigned)max(ya - 1, 0) * (unsigned)W + (unsigned)xc) * 4u;   // byte offset of the row being loaded
-    float vn[6];                                     // next row's samples, loaded one iteration ahead
+    constexpr int NP = LAZY ? 5 : 6;                 // planes streamed
+    float vn[NP];                                    // next row's samples, loaded one iteration ahead
     if (active) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) vn[k] = ld(k, off);
+        for (int k = 0; k < NP; k++) vn[k] = ld(k, off);
     } else {
 #pragma unroll
-        for (int k = 0; k < 6; k++) vn[k] = 0.f;
+        for (int k = 0; k < NP; k++) vn[k] = 0.f;
     }
     for (int y = ya - 1; y <= yb; y++) {
-        float v[6];
+        float v[NP];
 #pragma unroll
-        for (int k = 0; k < 6; k++) v[k] = vn[k];
+        for (int k = 0; k < NP; k++) v[k] = vn[k];
         if (y < yb) {
             off += pitch;
 #pragma unroll
-            for (int k = 0; k < 6; k++) vn[k] = ld(k, off);
+            for (int k = 0; k < NP; k++) vn[k] = ld(k, off);
         }
         float d[5];
 #pragma unroll
-        for (int k = 0; k < 5; k++) d[k] = v[k] - v[k + 1];
+        for (int k = 0; k < NP - 1; k++) d[k] = v[k] - v[k + 1];
+        if (LAZY) d[4] = d[3];                       // never beyond max / min (d[2], d[3]): scale 3 is tested against 18 neighbours
         // shift rolling window
 #pragma unroll
         for (int k = 0; k < 3; k++) { hM[0][k] = hM[1][k]; hM[1][k] = hM[2][k]; hm[0][k] = hm[1][k]; hm[1][k] = hm[2][k]; }
@@ -232,7 +237,7 @@ __device__ __forceinline__ void extrema_strip(const BlurPlanes &b, int W, int H,
 
 // (the fused-refinement form is the one of small planes, a latency chain of few workgroups: it takes the registers it
 // needs -- at the five-wave budget it spilled four to scratch)
-template <bool REFINE>
+template <bool REFINE, bool LAZY = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REFINE ? 4 : SIFT_EXT_WAVES, 8))) void extrema_kernel(BlurPlanes b, int W, int H, int border, int rows, double contrast,
                                                       float edth, float4 *__restrict__ cand,
                                                       int *__restrict__ counter, int capacity, RefineArgs ra,
@@ -249,7 +254,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REFINE ? 4 
     const int wid = wg * 4 + (threadIdx.x >> 6);
     const bool active = wid < nx * ny;                   // no early exit: the workgroup meets at the end
     int pending = 0;                                     // candidates parked in L.buf (wave uniform)
-    extrema_strip<SIFT_EXT_BUF, REFINE>(b, W, H, border, rows, active, active ? wid % nx : 0, active ? wid / nx : 0, contrast, edth, cand,
+    extrema_strip<SIFT_EXT_BUF, REFINE, LAZY>(b, W, H, border, rows, active, active ? wid % nx : 0, active ? wid / nx : 0, contrast, edth, cand,
                                         counter, capacity, L, pending, &ra, y_lo, y_hi);
     if (REFINE) return;                                  // every survivor is already in the keypoint list
     // ---- what is left leaves with one atomicAdd per workgroup
@@ -292,6 +297,9 @@ __device__ __forceinline__ void refine_candidates(const BlurPlanes &b, int W, in
         if (scale == 2) { Pa = b.p[1]; Pb = b.p[2]; Pc = b.p[3]; Pd = b.p[4]; }
         else if (scale == 3) { Pa = b.p[2]; Pb = b.p[3]; Pc = b.p[4]; Pd = b.p[5]; }
         // P = DoG[scale-1] = Pa-Pb, D = DoG[scale] = Pb-Pc, N = DoG[scale+1] = Pc-Pd
+        // (At most 5 moves of +-1 per axis, and the N layer is read at the current centre +-1: a scale-3 candidate reads
+        // plane 5 within Chebyshev distance 6 of where it was found -- the 13 x 13 patch top_patch_kernel writes around it,
+        // k_top_patch.hpp: SIFT_TOP_R.  Changing `moves` or the stencil changes that radius.)
         int newr = r, newc = c, moves = 5;
         bool again = true;
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, peak = 0.f;

@@ -28,6 +28,7 @@
 #include "k_stack_clip.hpp"
 #include "k_pyramid.hpp"
 #include "k_tail.hpp"
+#include "k_top_patch.hpp"
 #include "siftmath.hpp"
 
 using namespace siftk;
@@ -138,6 +139,13 @@ struct Options {
     int desc_early_blocks = 704;   // descriptor workgroups of a small octave 0 when the later octaves started early (they are nearly done by
                                    // then: 576 leaves room nobody needs, 960 starves what is left; 640 / 704 / 768 / 832: 0.797 / 0.785 / 0.788-0.799 / 0.801)
     int fused_refine = 1;    // detection and refinement in one launch: 0 never, 1 planes below 1400^2, 2 every plane
+    // The top plane (plane 5) only around scale-3 candidates: octaves whose detection keeps a candidate list skip the blur launch
+    // that writes plane 5, run the lazy extrema instance and top_patch_kernel (k_top_patch.hpp).  0 never, 1 always, 2 when the
+    // previous image of this plan left fewer than one scale-3 candidate per `lazy_density` pixels in that octave (a plan's first
+    // image is eager).  Same records either way.  lazy_density: DESIGN_APPENDIX, "Lazy top plane: the density sweep".  Set
+    // through siftmi_plan_set_lazy_top.
+    int lazy_top = 2, lazy_density = 6000;
+    int top_blocks = 8192;   // workgroups (waves) of top_patch_kernel: one list entry each, grid stride
     int fused_shrink = 1;    // octave hand-off inside the blur launch that writes plane 3 (512^2 frame -4 %, 2048^2 -4 %, 4096^2 +-0)
     int ori_team = 1024;     // groups with fewer refined keypoints than this: a workgroup per keypoint in the orientation launch (0: never)
     int desc_dynamic = 1;    // wave-per-keypoint form: keypoints beyond each wave's first are handed out through a device counter
@@ -255,6 +263,11 @@ struct siftmi_plan {
     int last_tail_first = 0;                  // tail_first_cur of the run that produced the result
     int last_n_cand[SIFT_MAX_OCTAVES] = {0};
     int last_c_scale[SIFT_MAX_OCTAVES][3] = {{0}};
+    // lazy top plane (option "lazy_top"): the octaves of the image being enqueued / of the last finished call whose plane 5 holds
+    // patches only (siftmi_plan_planes completes it); a call has finished on this plan (the auto rule has counts to go by);
+    // the image in flight outran a candidate list with provisional entries in it and runs again eagerly
+    bool lazy_cur[SIFT_MAX_OCTAVES] = {false}, lazy_last[SIFT_MAX_OCTAVES] = {false}, lazy_ran[SIFT_MAX_OCTAVES] = {false};
+    bool lazy_seen = false, lazy_block = false;
     std::vector<void *> allocs;
 
     template <class T> int alloc(T **p, size_t nbytes) {
@@ -543,13 +556,24 @@ DetectGeom detect_geometry(int W, int H, int border, int rows_opt, int min_strip
     return g;
 }
 
-// extrema_kernel: `refine` picks the instance that also refines the survivors of the edge test (ra: where they go)
+// extrema_kernel: `refine` picks the instance that also refines the survivors of the edge test (ra: where they go); `lazy` the
+// one that does not read bp.p[5] and leaves provisional scale-3 candidates (list form only; launch_top_patch follows it)
 void launch_extrema(hipStream_t st, bool refine, const DetectGeom &geo, const BlurPlanes &bp, int W, int H, int border, double contrast, float edth,
-                    float4 *cand, int *n_cand, int cand_cap, const RefineArgs &ra, int y_lo, int y_hi, int xcd_map) {
+                    float4 *cand, int *n_cand, int cand_cap, const RefineArgs &ra, int y_lo, int y_hi, int xcd_map, bool lazy = false) {
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)geo.blocks), dim3(256), 0, st, bp, W, H, border, geo.rows, contrast, edth, cand, n_cand, cand_cap, ra, y_lo, y_hi, xcd_map);
     };
-    if (refine) go(extrema_kernel<true>); else go(extrema_kernel<false>);
+    if (refine) go(extrema_kernel<true>); else if (lazy) go(extrema_kernel<false, true>); else go(extrema_kernel<false>);
+}
+
+// top_patch_kernel over the candidate list of one octave: plane 5 (`p5`, written) from plane 4 with the top plane's taps around
+// every scale-3 entry, `blocks` one-wave workgroups striding over the device-side count
+int launch_top_patch(hipStream_t st, int blocks, const float *p4, float *p5, int W, int H, const Taps &t, float4 *cand, const int *n_cand, int cand_cap) {
+    if (t.n < 1 || t.n > 64) return fail(SIFTMI_EINVAL, "top_patch_kernel takes 1..64 taps, not %d", t.n);
+    TopTaps ta;
+    for (int i = 0; i < 64; i++) ta.t[i] = i < t.n ? t.t[i] : 0.0f;
+    hipLaunchKernelGGL(top_patch_kernel, dim3((unsigned)blocks), dim3(64), top_patch_lds_bytes(t.n), st, p4, p5, W, H, ta, t.n, cand, n_cand, cand_cap);
+    return SIFTMI_OK;
 }
 
 // refine_kernel over the candidate list of one octave, `blocks` workgroups
@@ -718,6 +742,24 @@ int group_of(const siftmi_plan *p, int oct) { return oct == 0 ? 0 : ((oct == 1 &
 // "split" octave 1 is searched beside the octaves below it, so its candidates take group 1's otherwise unused buffer.
 int cand_group_of(const siftmi_plan *p, int oct) { return (oct == 1 && p->split_cur) ? 1 : group_of(p, oct); }
 
+// One launch detects and refines an octave (launch_detect_octave) or two do
+bool detect_fused(const siftmi_plan *p, int oct) {
+    return p->profile <= 1 && (p->opt.fused_refine == 2 || (p->opt.fused_refine == 1 && !march_plane(p->ow[(size_t)oct], p->oh[(size_t)oct])));
+}
+
+// Does octave `oct` of the image being enqueued go without its full plane 5 (option "lazy_top")?  Only an octave with a
+// per-octave pyramid and a candidate list (the fused detect-and-refine form reads plane 5 as it parks; the tail kernel builds
+// its own planes), not under the full profile (every stage keeps its launch and label), not in the run that repeats an image
+// whose provisional entries outran the candidate list.  Auto: by the scale-3 candidates this octave had in the previous image.
+bool lazy_octave(const siftmi_plan *p, int oct, int tail_first) {
+    const int mode = p->opt.lazy_top;
+    if (!mode || p->lazy_block || p->profile > 1 || oct >= tail_first || oct >= SIFT_MAX_OCTAVES || detect_fused(p, oct)) return false;
+    const int W = p->ow[(size_t)oct], H = p->oh[(size_t)oct], border = p->par.border_dist;
+    if (!(W > 2 * border && H > 2 * border)) return false;
+    if (mode == 1) return true;
+    return p->lazy_seen && (long long)p->last_c_scale[oct][2] * p->opt.lazy_density < (long long)W * H;
+}
+
 // Extrema of the three detection scales + sub-pixel refinement of one octave; survivors are appended to the refined list
 // of the octave's group (tagged with the octave).
 void launch_detect_octave(siftmi_plan *p, int oct, hipStream_t st) {
@@ -738,13 +780,19 @@ void launch_detect_octave(siftmi_plan *p, int oct, hipStream_t st) {
     // One launch detects and refines (the survivors of the edge test are refined by the wave that parked them: no
     // candidate list, no second launch) unless every stage is bracketed on its own (full profile) or option
     // "fused_refine" says otherwise (0: never, 1: planes below 1400^2, 2: every plane).
-    const bool fused = p->profile <= 1 && (p->opt.fused_refine == 2 || (p->opt.fused_refine == 1 && !march_plane(W, H)));
+    const bool fused = detect_fused(p, oct);
+    const bool lazy = oct < SIFT_MAX_OCTAVES && p->lazy_cur[oct];        // (never with `fused`: lazy_octave)
     {
         snprintf(lab, sizeof lab, fused ? "local_maxmin+interp_keypoint %d" : "local_maxmin %d", oct);
         Scope sc(p, lab, false, 0, st);
-        launch_extrema(st, fused, geo, bp, W, H, border, contrast_threshold(p->par), octave_edge_thresh(p->par, 1 << oct), GC.cand, n_cand, ccap, ra, -1, -1, p->opt.xcd_map);
+        launch_extrema(st, fused, geo, bp, W, H, border, contrast_threshold(p->par), octave_edge_thresh(p->par, 1 << oct), GC.cand, n_cand, ccap, ra, -1, -1, p->opt.xcd_map, lazy);
     }
     if (fused) return;
+    if (lazy) {     // plane 5 around the provisional scale-3 candidates, and the outer layer of their test (k_top_patch.hpp)
+        snprintf(lab, sizeof lab, "top_patch %d", oct);
+        Scope sc(p, lab, false, 0, st);
+        (void)launch_top_patch(st, p->opt.top_blocks, p->plane(oct, 4), p->plane(oct, 5), W, H, p->taps[4], GC.cand, n_cand, ccap);
+    }
     snprintf(lab, sizeof lab, "interp_keypoint+compact %d", oct);
     Scope sc(p, lab, false, 0, st);
     launch_refine(st, 512, bp, W, H, GC.cand, n_cand, ccap, ra);
@@ -1112,6 +1160,18 @@ int siftmi_plan_set_option(siftmi_plan *p, const char *name, int64_t value) {
     return SIFTMI_OK;
 }
 
+// The lazy top plane of a plan (Options::lazy_top and its two tuning values; see include/siftmi.h).  An entry point of its own:
+// mode, threshold and grid are set together, and a value <= 0 of the latter two keeps what the plan has.
+int siftmi_plan_set_lazy_top(siftmi_plan *p, int32_t mode, int32_t density, int32_t blocks) {
+    if (!p) return fail(SIFTMI_EINVAL, "null plan");
+    if (mode < 0 || mode > 2) return fail(SIFTMI_EINVAL, "lazy_top must be 0 (never), 1 (always) or 2 (by the previous image)");
+    if (blocks > 65535) return fail(SIFTMI_EINVAL, "top_patch_kernel takes at most 65535 workgroups");
+    p->opt.lazy_top = mode;
+    if (density > 0) p->opt.lazy_density = density;
+    if (blocks > 0) p->opt.top_blocks = blocks;
+    return SIFTMI_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1215,6 +1275,7 @@ int enqueue_body(siftmi_plan *p) {
     const int tail_first = tail_first_octave(p);
     p->tail_first_cur = tail_first;
     p->groups_cur = 0;
+    for (int o = 0; o < SIFT_MAX_OCTAVES; o++) p->lazy_cur[o] = o < p->n_oct && lazy_octave(p, o, tail_first);
     for (hipStream_t &w : p->wait_s) w = nullptr;
     // Gradient maps for the per-keypoint kernels of this image (option "maps"): large frames, by the previous image's counts
     {
@@ -1292,7 +1353,14 @@ int enqueue_body(siftmi_plan *p) {
             p->chain = ch;
         }
         bool pyr0_bound = false;
-        for (int s = 0; s < 5; s++) {
+        // lazy top plane: the launch that writes plane 5 is not run; what rode on it rides on the one that writes plane 4
+        const bool lazy = oct < SIFT_MAX_OCTAVES && p->lazy_cur[oct];
+        const int s_last = lazy ? 3 : 4;
+        if (lazy && oct == 0 && p->profile == 1 && p->chain) {
+            Scope *ch = static_cast<Scope *>(p->chain);
+            if (ch->idx != (size_t)-1) { p->events[ch->idx].launches -= 1; p->events[ch->idx].pixels -= (double)W * H; }
+        }
+        for (int s = 0; s <= s_last; s++) {
             if (p->profile > 1) snprintf(lab, sizeof lab, "Blur octave %d scale %d (%d taps)", oct, s, p->taps[s].n);
             // the events other streams (or the light profile) wait for are the END of a blur launch: they ride on it (launch_ev)
             hipEvent_t done = nullptr;
@@ -1301,10 +1369,10 @@ int enqueue_body(siftmi_plan *p) {
                 done = p->ev_early;
             } else if (s == 2 && oct == 1 && (fork || split)) {
                 done = p->ev_p3;       // plane 3 of octave 1 and plane 0 of octave 2 exist (or will be shrunk from it): the chain below starts here
-            } else if (s == 4 && oct == 0 && p->profile == 1 && p->chain) {
+            } else if (s == s_last && oct == 0 && p->profile == 1 && p->chain) {
                 Scope *ch = static_cast<Scope *>(p->chain);
                 if (ch->idx != (size_t)-1) { done = p->events[ch->idx].b; ch->stop_bound = true; }     // closes the light profile's bracket
-            } else if (s == 4 && oct == 0 && p->profile == 0 && two) {
+            } else if (s == s_last && oct == 0 && p->profile == 0 && two) {
                 done = p->ev_pyr[0]; pyr0_bound = true;
             }
             {
@@ -1474,6 +1542,13 @@ int plan_wait(siftmi_plan *p, int64_t *n_out, int32_t *overflow) {
         drain_streams(p);
         return fail(SIFTMI_ETAILRETRY, "octave_tail_kernel timed out waiting for the previous octave; tail launches disabled for this plan");
     }
+    // A candidate list with provisional scale-3 entries in it (lazy top plane) holds more than the eager form's: where it was
+    // cut, the image runs again eagerly, so that growth, the capacity rule and the cut act on the counts they are defined on.
+    for (int o = 0; o < p->n_oct && o < SIFT_MAX_OCTAVES; o++)
+        if (p->lazy_cur[o] && hc.n_cand[o] > p->grp[cand_group_of(p, o)].cap_cand) {
+            p->lazy_block = true;
+            return fail(SIFTMI_EGROW, "provisional candidates outran the list; the image runs again with the full top plane");
+        }
     {
         // a list that was cut at its buffer's size: grow it and run the image again (what lies behind the cut was never made)
         bool grown = false;
@@ -1511,7 +1586,13 @@ int plan_wait(siftmi_plan *p, int64_t *n_out, int32_t *overflow) {
     for (int o = 0; o < SIFT_MAX_OCTAVES; o++) {
         p->last_n_cand[o] = hc.n_cand[o] + (o == 0 ? hc.n_cand[SIFT_MAX_OCTAVES] : 0);   // (the slot of a split octave 0 belongs to octave 0)
         for (int s = 0; s < 3; s++) p->last_c_scale[o][s] = hc.c_scale[o][s];
+        // lazy top plane: the list also held the provisional entries top_patch_kernel turned into holes; the candidates are what
+        // the refinement read (the list was not cut: see above)
+        if (p->lazy_cur[o]) p->last_n_cand[o] = hc.c_scale[o][0] + hc.c_scale[o][1] + hc.c_scale[o][2];
+        p->lazy_last[o] = p->lazy_ran[o] = p->lazy_cur[o];      // (lazy_last is cleared when siftmi_plan_planes completes the plane)
     }
+    p->lazy_seen = true;
+    p->lazy_block = false;
     p->last_valid = true;
     p->last_group0 = (int)std::min<int64_t>(hc.g_out[0], n);
     p->last_group1 = (int)n - p->last_group0;
@@ -1601,8 +1682,9 @@ int siftmi_plan_fetch(siftmi_plan *p, siftmi_keypoint *out, int32_t out_is_devic
     return SIFTMI_OK;
 }
 
-// The six blur planes of one octave as the last finished call left them (see include/siftmi.h).  Nothing is launched: the
-// plan's streams are waited for (they are idle after plan_wait) and the planes are copied out.
+// The six blur planes of one octave as the last finished call left them (see include/siftmi.h).  The plan's streams are waited
+// for (they are idle after plan_wait) and the planes are copied out; nothing is launched but the top plane's blur of an
+// octave that went without it (option "lazy_top").
 int siftmi_plan_planes(siftmi_plan *p, int32_t octave, float *out, int64_t capacity, int32_t *width, int32_t *height) {
     if (!p) return fail(SIFTMI_EINVAL, "null plan");
     if (!out) return fail(SIFTMI_EINVAL, "null output buffer");
@@ -1614,10 +1696,25 @@ int siftmi_plan_planes(siftmi_plan *p, int32_t octave, float *out, int64_t capac
     HIPCHK(hipSetDevice(p->device));
     for (hipStream_t s : {p->stream2, p->stream3})
         if (s) HIPCHK(hipStreamSynchronize(s));
+    if (octave < SIFT_MAX_OCTAVES && p->lazy_last[octave]) {
+        // the last call wrote plane 5 of this octave only around its scale-3 candidates (option "lazy_top"): the launch it
+        // went without runs now (the patches hold the same bits)
+        launch_blur(p, p->plane(octave, 4), p->plane(octave, 5), W, H, p->taps[4], false, p->stream);
+        p->lazy_last[octave] = false;
+    }
     HIPCHK(hipMemcpyAsync(out, p->plane(octave, 0), (size_t)need * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     if (width) *width = W;
     if (height) *height = H;
+    return SIFTMI_OK;
+}
+
+// Which octaves of the last finished call went without their full plane 5 (option "lazy_top"); see include/siftmi.h
+int siftmi_plan_lazy_octaves(const siftmi_plan *p, int32_t *lazy, int32_t n_octaves) {
+    if (!p || !lazy) return fail(SIFTMI_EINVAL, "null argument");
+    if (n_octaves < p->n_oct) return fail(SIFTMI_EINVAL, "room for %d octaves, the plan has %d", n_octaves, p->n_oct);
+    if (!p->last_valid || p->in_flight) return fail(SIFTMI_EINVAL, "the plan has not finished a call");
+    for (int o = 0; o < p->n_oct; o++) lazy[o] = (o < SIFT_MAX_OCTAVES && p->lazy_ran[o]) ? 1 : 0;
     return SIFTMI_OK;
 }
 
@@ -2759,6 +2856,66 @@ int siftmi_stage_detect_ex(int32_t dev, const float *blurs, int32_t W, int32_t H
     HIPCHK(hipMemcpy(cand, c.p, cslots * 16, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(kp, k.p, kslots * 16, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(kp_aux, ka.p, kslots * 4, hipMemcpyDeviceToHost));
+    return SIFTMI_OK;
+}
+
+// The lazy detection chain of launch_detect_octave on five planes: extrema(LAZY) -> top_patch_kernel -> refinement.  Plane 5
+// is allocated here and filled with a NaN pattern, so that a read outside the patches turns what it feeds into NaN.
+int siftmi_stage_detect_lazy(int32_t dev, const float *blurs5, const float *top_taps, int32_t n_taps, int32_t W, int32_t H, int32_t octsize,
+                             const siftmi_params *par, int32_t rows, int32_t xcd_map, int32_t y_lo, int32_t y_hi,
+                             int64_t cand_capacity, int64_t kp_capacity, float *cand, float *kp, int32_t *kp_aux, int32_t *counters, float *plane5) {
+    int rc = stage_begin(dev); if (rc) return rc;
+    if (!blurs5 || !top_taps || !par || !counters || !cand || !kp || !kp_aux || !plane5) return fail(SIFTMI_EINVAL, "null argument");
+    if (W < 1 || H < 1) return fail(SIFTMI_EINVAL, "empty plane");
+    if (n_taps < 1 || n_taps > 64) return fail(SIFTMI_EINVAL, "1..64 taps, not %d", n_taps);
+    if (rows < 0 || rows > 4096) return fail(SIFTMI_EINVAL, "strip rows must be in 0..4096 (0: by the size rule)");
+    if (cand_capacity < 0 || kp_capacity < 0 || cand_capacity > (1 << 30) || kp_capacity > (1 << 30)) return fail(SIFTMI_EINVAL, "capacity out of range");
+    const int border = par->border_dist;
+    if (border < 1) return fail(SIFTMI_EINVAL, "border_dist must be at least 1 (the 3 x 3 neighbourhood)");
+    const bool band = y_lo >= 0;
+    if (band && !(y_lo >= border && y_lo < y_hi && y_hi <= H - border))
+        return fail(SIFTMI_EINVAL, "band [%d, %d) outside the detection rows [%d, %d)", y_lo, y_hi, border, H - border);
+    int oct;
+    if ((rc = stage_octave(octsize, oct))) return rc;
+    const size_t N = (size_t)W * H;
+    const size_t cslots = (size_t)cand_capacity + SIFTMI_STAGE_GUARD, kslots = (size_t)kp_capacity + SIFTMI_STAGE_GUARD;
+    DevBuf b, c, k, ka, cnt;
+    if ((rc = b.alloc(6 * N * 4)) || (rc = c.alloc(cslots * 16)) || (rc = k.alloc(kslots * 16)) ||
+        (rc = ka.alloc(kslots * 4)) || (rc = cnt.alloc(sizeof(Counters)))) return rc;
+    HIPCHK(hipMemcpy(b.p, blurs5, 5 * N * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(cnt.p, 0, sizeof(Counters)));
+    {
+        std::vector<uint32_t> fill(N, SIFTMI_STAGE_TOP_FILL);
+        HIPCHK(hipMemcpy(b.as<float>() + 5 * N, fill.data(), N * 4, hipMemcpyHostToDevice));
+        std::vector<float> holes(cslots * 4, -1.0f);
+        HIPCHK(hipMemcpy(c.p, holes.data(), cslots * 16, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemset(k.p, 0xa5, kslots * 16));
+    HIPCHK(hipMemset(ka.p, 0xa5, kslots * 4));
+    BlurPlanes bp;
+    for (int s = 0; s < 6; s++) bp.p[s] = b.as<float>() + (size_t)s * N;
+    Counters *dc = cnt.as<Counters>();
+    const int yl = band ? y_lo : -1, yh = band ? y_hi : -1;
+    const DetectGeom geo = detect_geometry(W, H, border, rows, g_default_options.ext_strips, yl, yh);
+    if (geo.blocks) {
+        Taps tp;
+        tp.n = n_taps;
+        for (int i = 0; i < n_taps; i++) tp.t[i] = top_taps[i];
+        const RefineArgs ra = {par->peak_thresh, (float)par->init_sigma, k.as<float4>(), ka.as<int>(), &dc->g_kp[0], (int)kp_capacity, oct, &dc->c_scale[0][0]};
+        launch_extrema(0, false, geo, bp, W, H, border, contrast_threshold(*par), octave_edge_thresh(*par, octsize), c.as<float4>(),
+                       &dc->n_cand[0], (int)cand_capacity, ra, yl, yh, xcd_map ? 1 : 0, true);
+        if ((rc = launch_top_patch(0, g_default_options.top_blocks, bp.p[4], b.as<float>() + 5 * N, W, H, tp, c.as<float4>(), &dc->n_cand[0], (int)cand_capacity))) return rc;
+        launch_refine(0, 512, bp, W, H, c.as<float4>(), &dc->n_cand[0], (int)cand_capacity, ra);
+    }
+    if ((rc = stage_end())) return rc;
+    Counters hc;
+    HIPCHK(hipMemcpy(&hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost));
+    counters[0] = hc.n_cand[0]; counters[1] = hc.g_kp[0];
+    for (int s = 0; s < 3; s++) counters[2 + s] = hc.c_scale[0][s];
+    HIPCHK(hipMemcpy(cand, c.p, cslots * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(kp, k.p, kslots * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(kp_aux, ka.p, kslots * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(plane5, b.as<float>() + 5 * N, N * 4, hipMemcpyDeviceToHost));
     return SIFTMI_OK;
 }
 

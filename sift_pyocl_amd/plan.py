@@ -138,6 +138,7 @@ class SiftPlan(object):
         self._profile_level = 0 if not profile else (1 if profile == "light" else 2)
         self.events = []
         self._sem = threading.Semaphore()
+        self._lazy_top = {"lazy_top": 2, "lazy_density": 0, "top_blocks": 0}     # (0: the library's value)
         self.scales = []     # octave sizes in XY order, as the reference
         self.procsize = []
         self.wgsize = []
@@ -357,10 +358,20 @@ class SiftPlan(object):
 
     __call__ = keypoints
 
+    _LAZY_TOP = ("lazy_top", "lazy_density", "top_blocks")
+
     def set_option(self, name, value):
         """Tuning / diagnostic option of the device plan by name (``siftmi_plan_set_option`` in include/siftmi.h);
         results never depend on an option."""
-        _lib.check(_lib.lib().siftmi_plan_set_option(self._handle, str(name).encode(), int(value)))
+        name = str(name)
+        if name in self._LAZY_TOP:       # the lazy top plane has an entry point of its own (siftmi_plan_set_lazy_top)
+            if name != "lazy_top" and int(value) < 1:
+                raise RuntimeError("%s must be >= 1" % name)
+            self._lazy_top[name] = int(value)
+            _lib.check(_lib.lib().siftmi_plan_set_lazy_top(self._handle, self._lazy_top["lazy_top"], self._lazy_top["lazy_density"],
+                                                          self._lazy_top["top_blocks"]))
+            return
+        _lib.check(_lib.lib().siftmi_plan_set_option(self._handle, name.encode(), int(value)))
 
     def capacity(self):
         """(records the device list holds now, times a list has grown).  The lists start at ``kpsize`` entries -- the
@@ -387,7 +398,8 @@ class SiftPlan(object):
 
     def planes(self, octave):
         """The six blur planes of `octave` as the last finished keypoints() call left them on the device: (6, H, W) float32,
-        scale 0 first (the reference's buffers["scale_<octave>_<scale>"]).  Nothing is launched; valid until the next call."""
+        scale 0 first (the reference's buffers["scale_<octave>_<scale>"]).  Valid until the next call.  (An octave that ran
+        without its full top plane -- option ``lazy_top`` -- gets that one blur launch first.)"""
         octave = int(octave)
         if not 0 <= octave < self.octave_max:
             raise RuntimeError("octave %d outside 0..%d" % (octave, self.octave_max - 1))
@@ -398,6 +410,15 @@ class SiftPlan(object):
             _lib.check(_lib.lib().siftmi_plan_planes(self._handle, octave, out.ctypes.data, out.size, C.byref(gw), C.byref(gh)))
         assert (gw.value, gh.value) == (w, h)
         return out
+
+    def lazy_octaves(self):
+        """Per octave, whether the last finished keypoints() call ran the lazy detection chain (plan option ``lazy_top``: the
+        top blur plane only around scale-3 candidates).  ``planes()`` returns whole planes either way."""
+        n = int(self.octave_max)
+        flags = numpy.zeros(max(n, 1), numpy.int32)
+        with self._sem:
+            _lib.check(_lib.lib().siftmi_plan_lazy_octaves(self._handle, flags.ctypes.data, n))
+        return [bool(v) for v in flags[:n]]
 
     def last_counts(self):
         """Host integers of the last finished keypoints() call: dict(tail_first = first octave the one-launch form of the
