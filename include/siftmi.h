@@ -405,6 +405,52 @@ int siftmi_batch_stack_clip_ex(siftmi_batch *batch, const void *const *images, i
                                const float *maps /* n x 6 */, const float *fills /* n */, const float *weights /* n, or null */,
                                int32_t mode, int32_t interp, int32_t reject, int32_t n_low, int32_t n_high, float kappa_low,
                                float kappa_high, int32_t iters, float empty, double *kernel_ms);
+/* A stack of any length, chunk after chunk (extension; DESIGN.md section 7 row 20, restated in numpy by
+ * tests/stack_accum_ref.py; kernels in csrc/k_stack_accum.hpp).  The caller owns per-pixel running sums on the device; every call
+ * adds one chunk of frames to them, a last call turns them into mean and variance.  Device memory is one chunk of frames plus 16
+ * to 24 bytes per output pixel, whatever the length of the stack.
+ * siftmi_batch_stack_accum  warps n float32 frames as siftmi_batch_stack_ex does (v_s, live_s; `interp` as there) and adds them
+ *                         into the state planes in one launch (stack_accum_kernel).  Per output pixel o, one rounding per
+ *                         operation:
+ *                           clip    given when `center` and `var` are not null: m = center[o], tl = (kappa_low * kappa_low) * var[o],
+ *                                   th = (kappa_high * kappa_high) * var[o], all binary32
+ *                           for s ascending, live frames only:
+ *                             coverage[o] += 1
+ *                             clip:  d = v_s - m; q = d * d; rejected = (d < 0 && q > tl) || (d > 0 && q > th)      (binary32)
+ *                             not rejected:  s1[o] = s1[o] + (double)v_s;  s2[o] = s2[o] + (double)v_s * (double)v_s (the product
+ *                                   is exact in binary64);  kept[o] += 1
+ *                         A NaN in the sample, the centre, the variance or a threshold (inf * 0) makes the comparisons false:
+ *                         nothing is rejected -- a pixel that a first pass left `empty` = NaN rejects nothing.  var[o] == 0 with
+ *                         finite kappas rejects every sample that differs from the centre; kappa = +inf switches its side off.
+ *                         This is siftmi_batch_stack_clip's SIGMA rule with the statistics supplied from outside: a second pass
+ *                         over the frames with the first pass's mean and variance is a sigma clip of a stack of any length.
+ *                         Any split of a stack into calls gives the same state bit for bit.
+ *   images, maps, fills, mode, interp   as for siftmi_batch_stack_ex (host frames staged the same way)
+ *   s1, s2       OH x OW binary64, device; s2 may be NULL (no second moments: no variance later)
+ *   coverage, kept   OH x OW int32, device.  All state planes are contiguous, owned by the caller and zero-filled by the caller
+ *                before the first call
+ *   center, var  OH x OW float32, device, both or neither
+ *   kernel_ms    optional, hipEvent duration of the launch (0 when nothing is launched)
+ * siftmi_batch_stack_accum_result   one launch (stack_accum_result_kernel), per pixel: k = kept[o]; k == 0: mean = var = `empty`;
+ *                         else M = s1[o] / (double)k; mean = (float)M; V = s2[o] / (double)k - M * M; var = (float)(V < 0 ? 0 : V).
+ *                         The population variance, as the SIGMA rule's q / n; no square root is taken, the clip takes the variance.
+ *   s1, s2, kept  the state, device; s2 may be NULL when `var` is
+ *   mean, var    OH x OW float32, host (staged in the batch's buffer, the variance behind the mean) or device (out_is_device);
+ *                var may be NULL
+ * Each call is one launch and one synchronisation.  The state, `center` and `var` are device pointers, ordered after the caller's
+ * streams as everywhere: both calls synchronise the device once on entry.  n_images == 0 or an empty output launches nothing,
+ * leaves the state untouched and returns 0.  SIFTMI_EINVAL, nothing launched and nothing written: everything
+ * siftmi_batch_stack_ex refuses about the handle, frames, tables, shape and sampler (a batch created for RGB8 and
+ * SIFTMI_INTERP_CUBIC with mode != 1 included); a null s1, coverage, kept or mean with work to do; exactly one of `center` and `var`
+ * null; with a clip, a kappa that is NaN or <= 0; `var` asked of the result with s2 null. */
+int siftmi_batch_stack_accum(siftmi_batch *batch, const void *const *images, int32_t n_images, int32_t images_are_device,
+                             double *s1, double *s2 /* may be null */, int32_t *coverage, int32_t *kept,
+                             int32_t out_width, int32_t out_height, const float *maps /* n x 6 */, const float *fills /* n */,
+                             int32_t mode, int32_t interp, const float *center /* device, or null */,
+                             const float *var /* device; null iff center is */, float kappa_low, float kappa_high, double *kernel_ms);
+int siftmi_batch_stack_accum_result(siftmi_batch *batch, const double *s1, const double *s2 /* may be null */, const int32_t *kept,
+                                    int32_t out_width, int32_t out_height, float *mean, float *var /* may be null; needs s2 */,
+                                    int32_t out_is_device, float empty, double *kernel_ms);
 
 /* ---- MatchPlan -----------------------------------------------------------------------------
  * siftmi_match_create <- MatchPlan.__init__ (match.py:77-139)

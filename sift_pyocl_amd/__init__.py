@@ -9,6 +9,6 @@ from .param import par
 from .plan import SiftPlan
 from .match import MatchPlan, ratio_filter
 from .alignment import LinearAlign
-from .batch import BatchPlan
+from .batch import BatchPlan, StackAccumulator
 
-__all__ = ["par", "SiftPlan", "MatchPlan", "ratio_filter", "LinearAlign", "BatchPlan", "version"]
+__all__ = ["par", "SiftPlan", "MatchPlan", "ratio_filter", "LinearAlign", "BatchPlan", "StackAccumulator", "version"]

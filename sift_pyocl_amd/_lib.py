@@ -138,6 +138,12 @@ _SIGNATURES = {
     "siftmi_batch_stack_clip_ex": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float, C.POINTER(C.c_double)]),
+    # the streaming accumulator: state planes, centre and variance are device addresses
+    "siftmi_batch_stack_accum": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_double)]),
+    "siftmi_batch_stack_accum_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_int32, C.c_float, C.POINTER(C.c_double)]),
     "siftmi_match_set_roi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "siftmi_match_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -651,6 +651,98 @@ class LinearAlign(object):
             res.update(rest())
             return res
 
+    def stack_stream(self, images, chunk=32, reject=None, kappa=(3.0, 3.0), var=False, max_shift=None, expected_shift=None, shift_only=False,
+                     robust=False, robust_tol=3.0, robust_hyp=2048, match_ratio=None, empty=numpy.nan, return_all=False, out="host",
+                     lanes=None, *, interp=None):
+        """``stack(reduce="mean")`` for a stack of any length (extension): the frames are read in slices
+        of `chunk`, each slice is estimated as ``stack`` estimates it and added to a ``StackAccumulator``.  Device memory is one
+        chunk of frames plus 16 to 24 bytes per output pixel; the mean is formed from float64 sums.  Greyscale aligners only.
+
+        ``reject="sigma"`` makes two passes.  The first keeps the mean and the variance of every pixel and the map of every frame;
+        the second reads the slices again, samples them with the kept maps -- detection and matching are not repeated -- and adds
+        only what lies within ``kappa[0]`` standard deviations below and ``kappa[1]`` above the first pass's mean
+        (``StackAccumulator.add(clip=...)``): one pass of ``stack_clip``'s sigma rule, without its cap of 64 frames.
+
+        :param images: a sequence with ``len()`` and slice indexing whose slices ``align_batch`` accepts: a list, an (S, H, W)
+                       array, a memmap
+        :param chunk: frames per slice, >= 1
+        :param reject: None or ``"sigma"``
+        :param kappa: (kappa_low, kappa_high), each > 0; ``inf`` switches its side off
+        :param var: also return the population variance of the kept samples of every pixel (float32, not rooted)
+        :param max_shift, expected_shift, shift_only, robust, robust_tol, robust_hyp, match_ratio, empty, out, lanes, interp: as for
+                       ``stack``; an (S, 2) `expected_shift` is sliced with the frames
+        :param return_all: return a dict: ``stack``, ``coverage``, ``kept``, ``var`` if asked for, and ``matrix``, ``offset``,
+                       ``mode``, ``n``, ``rms``, ``fill`` of every frame, concatenated over the slices
+        :return: the combined image (OH, OW), ``(image, var)`` with `var`, or the dict
+        """
+        _lib.interp_code(interp, 1, self.RGB)
+        if self.RGB:
+            raise RuntimeError("stack_stream combines float32 frames; an RGB aligner has no stack reduction")
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        if reject not in (None, "sigma"):
+            raise ValueError("reject must be None or 'sigma', not %r" % (reject,))
+        if int(chunk) != chunk or chunk < 1:
+            raise ValueError("chunk must be a whole number >= 1, not %r" % (chunk,))
+        chunk = int(chunk)
+        try:
+            kl, kh = (float(numpy.float32(v)) for v in kappa)
+        except (TypeError, ValueError):
+            raise ValueError("kappa must be (kappa_low, kappa_high), not %r" % (kappa,))
+        if not (kl > 0 and kh > 0):
+            raise ValueError("kappa %r: each must be > 0 (inf switches its side off)" % (kappa,))
+        S = len(images)
+        shifts = None
+        if max_shift is None:
+            if expected_shift is not None:
+                raise ValueError("expected_shift needs max_shift")
+        else:
+            shifts = numpy.asarray((0.0, 0.0) if expected_shift is None else expected_shift, numpy.float64)
+        with self.sem:
+            bp = self._batch_plan(lanes)
+            first = bp.stack_accumulator(self.outshape, moments=bool(var) or reject == "sigma")
+            kept_maps, rests = [], []
+            total_ms = 0.0
+            for at in range(0, S, chunk):
+                if shifts is None:
+                    matcher = lambda ref, records, counts: self.match.match_batch(ref, None, records, counts, ratio=match_ratio, out="device")  # noqa: E731
+                else:
+                    shift = shifts[at:at + chunk] if shifts.ndim == 2 else shifts
+                    matcher = lambda ref, records, counts, shift=shift: self.match.match_window_batch(      # noqa: E731
+                        ref, None, records, counts, window=max_shift, window_shift=shift, ratio=match_ratio, out="device")
+                frames, matrix, offset, mode, fills, rest = self._estimate_batch(bp, images[at:at + chunk], matcher, shift_only, robust,
+                                                                                 robust_tol, robust_hyp)
+                first.add(frames, matrix, offset, fills, mode=1, interp=interp)
+                total_ms += first.last_stack_ms
+                kept_maps.append((matrix, offset, numpy.array(fills, numpy.float32)))
+                if return_all:
+                    rests.append(rest())
+                del frames
+            acc = first
+            if reject == "sigma":
+                center, spread = first.result(var=True, out="device")
+                acc = bp.stack_accumulator(self.outshape, moments=bool(var))
+                for i, at in enumerate(range(0, S, chunk)):
+                    matrix, offset, fills = kept_maps[i]
+                    frames = self._device_frames(images[at:at + chunk])
+                    acc.add(frames, matrix, offset, fills, mode=1, interp=interp, clip=(center, spread), kappa=(kl, kh))
+                    total_ms += acc.last_stack_ms
+                    del frames
+            planes = acc.result(empty=empty, var=bool(var), counts=True, out=out)
+            self.last_stack_ms = total_ms
+            if self.profile:
+                self.events.append(("stack_stream", StageEvent(total_ms)))
+            if not return_all:
+                return (planes[0], planes[1]) if var else planes[0]
+            res = {"stack": planes[0], "coverage": planes[-2], "kept": planes[-1]}
+            if var:
+                res["var"] = planes[1]
+            blank = {"matrix": numpy.zeros((0, 2, 2), numpy.float32), "offset": numpy.zeros((0, 2), numpy.float32), "mode": numpy.zeros(0, numpy.int8),
+                     "n": numpy.zeros(0, numpy.int64), "rms": numpy.zeros(0, numpy.float64), "fill": numpy.zeros(0, numpy.float32)}
+            for k, none in blank.items():
+                res[k] = numpy.concatenate([numpy.asarray(r[k]) for r in rests]) if rests else none
+            return res
+
     def _estimate_batch(self, bp, images, matcher, shift_only, robust, robust_tol, robust_hyp):
         """The estimate of every frame of a stack, shared by ``align_batch`` and ``stack`` (called with the semaphore held):
         ``(frames, matrix, offset, mode, fills, rest)`` -- the device frames, the (S, 2, 2) / (S, 2) maps (all NaN for a frame

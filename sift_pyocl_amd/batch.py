@@ -508,11 +508,155 @@ class BatchPlan(SiftPlan):
         del keep
         return (plane, cover, kept) if counts else plane
 
+    def stack_accumulator(self, out_shape=None, moments=False):
+        """A ``StackAccumulator`` on this plan: the streaming form of ``stack_batch`` for stacks that are longer than one call
+        should hold (``siftmi_batch_stack_accum``).  Greyscale plans only.
+
+        :param out_shape: (OH, OW) of the result; None: the plan's shape
+        :param moments: also keep the sum of squares, which ``result(var=True)`` needs
+        """
+        return StackAccumulator(self, out_shape, moments)
+
     def minmax(self):
         raise RuntimeError("BatchPlan keeps no per-frame min/max; use SiftPlan")
 
     def kernel_times(self):
         raise RuntimeError("BatchPlan does not collect per-stage events; profile a SiftPlan instead")
+
+
+class StackAccumulator(object):
+    """Per-pixel running sums of a stack that is fed chunk after chunk (``siftmi_batch_stack_accum``; DESIGN.md section 7 row
+    20), made by ``BatchPlan.stack_accumulator``.  The state lives on the plan's device as zeroed torch tensors: ``s1`` (float64,
+    the sum of the kept samples), ``s2`` (float64, the sum of their squares; with ``moments`` only), ``coverage`` and ``kept``
+    (int32).  Device memory is one chunk of frames plus 16 to 24 bytes per output pixel, whatever the length of the stack, and any
+    split of a stack into ``add`` calls gives the same state bit for bit.
+
+    Samples and live frames are ``stack_batch``'s.  Per output pixel and live frame, in the order of the frames: ``coverage += 1``;
+    with ``clip=(center, var)`` the sample ``v`` is rejected when ``d = v - center`` has ``d < 0 and d * d > kappa[0]**2 * var`` or
+    ``d > 0 and d * d > kappa[1]**2 * var`` (float32; a NaN anywhere rejects nothing); otherwise ``s1 += v``, ``s2 += v * v`` (float64)
+    and ``kept += 1``.  ``result`` gives ``s1 / kept`` and the population variance ``max(s2 / kept - mean**2, 0)``.  A first pass
+    with ``moments`` and a second one into a fresh accumulator with ``clip=first.result(var=True, out="device")`` is a sigma clip
+    of a stack of any length.
+    """
+
+    def __init__(self, plan, out_shape=None, moments=False):
+        import torch
+        if plan.RGB:
+            raise RuntimeError("a stack accumulator adds float32 frames; an RGB plan has no stack reduction")
+        oh, ow = (int(v) for v in (plan.shape if out_shape is None else out_shape))
+        if oh < 0 or ow < 0:
+            raise ValueError("negative output shape")
+        self.plan = plan
+        self.out_shape = (oh, ow)
+        self.moments = bool(moments)
+        dev = torch.device("cuda", plan.device)
+        self._s1 = torch.zeros((oh, ow), dtype=torch.float64, device=dev)
+        self._s2 = torch.zeros((oh, ow), dtype=torch.float64, device=dev) if self.moments else None
+        self._coverage = torch.zeros((oh, ow), dtype=torch.int32, device=dev)
+        self._kept = torch.zeros((oh, ow), dtype=torch.int32, device=dev)
+        #: the number of frames added so far
+        self.frames = 0
+        self.last_stack_ms = 0.0
+
+    def state(self):
+        """the live state tensors: ``s1``, ``coverage``, ``kept`` and, with moments, ``s2``"""
+        res = {"s1": self._s1, "coverage": self._coverage, "kept": self._kept}
+        if self.moments:
+            res["s2"] = self._s2
+        return res
+
+    def reset(self):
+        """zero the state: the accumulator is as it was made"""
+        for t in self.state().values():
+            t.zero_()
+        self.frames = 0
+
+    def _plane(self, plane, name):
+        """a clip plane as a contiguous float32 device tensor of the output's shape (host planes are uploaded)"""
+        import torch
+        dev = self._s1.device
+        if isinstance(plane, torch.Tensor):
+            if plane.dtype != torch.float32 or tuple(plane.shape) != self.out_shape:
+                raise ValueError("%s must be float32 %s, not %s %s" % (name, self.out_shape, plane.dtype, tuple(plane.shape)))
+            return plane.to(dev).contiguous()
+        plane = numpy.asarray(plane)
+        if plane.dtype != numpy.float32 or plane.shape != self.out_shape:
+            raise ValueError("%s must be float32 %s, not %s %s" % (name, self.out_shape, plane.dtype, plane.shape))
+        return torch.from_numpy(numpy.ascontiguousarray(plane)).to(dev)
+
+    def add(self, images, matrices, offsets, fills=0.0, mode=1, *, interp=None, clip=None, kappa=(3.0, 3.0)):
+        """Warp S more frames as ``stack_batch`` does and add them to the state in one launch.
+
+        :param images, matrices, offsets, fills, mode: as for ``stack_batch``
+        :param interp: as for ``stack_batch``
+        :param clip: None, or ``(center, var)``: two (OH, OW) float32 planes, numpy arrays (uploaded) or device tensors
+        :param kappa: (kappa_low, kappa_high) of the clip, each > 0; ``inf`` switches its side off
+        :return: the accumulator
+        """
+        plan = self.plan
+        code = _lib.interp_code(interp, mode, plan.RGB)
+        ptrs, n, is_dev, keep, maps, f, oh, ow = plan._warp_args(images, matrices, offsets, fills, self.out_shape, "device")
+        try:
+            kl, kh = (float(numpy.float32(v)) for v in kappa)
+        except (TypeError, ValueError):
+            raise ValueError("kappa must be (kappa_low, kappa_high), not %r" % (kappa,))
+        center = var = None
+        if clip is not None:
+            try:
+                center, var = clip
+            except (TypeError, ValueError):
+                raise ValueError("clip must be (center, var)")
+            center, var = self._plane(center, "the clip's centre"), self._plane(var, "the clip's variance")
+            if not (kl > 0 and kh > 0):
+                raise ValueError("kappa %r: each must be > 0 (inf switches its side off)" % (kappa,))
+        ms = C.c_double(0)
+        with plan._sem:
+            _lib.check(_lib.lib().siftmi_batch_stack_accum(
+                plan._handle, ptrs, n, is_dev, self._s1.data_ptr(), self._s2.data_ptr() if self.moments else None,
+                self._coverage.data_ptr(), self._kept.data_ptr(), ow, oh, maps.ctypes.data, f.ctypes.data, int(mode), code,
+                None if center is None else center.data_ptr(), None if var is None else var.data_ptr(), C.c_float(kl), C.c_float(kh),
+                C.byref(ms)))
+        self.last_stack_ms = plan.last_stack_ms = ms.value
+        self.frames += n
+        del keep, center, var
+        return self
+
+    def result(self, empty=numpy.nan, var=False, counts=False, out="host"):
+        """The mean of the kept samples of every pixel, `empty` where none was kept.
+
+        :param empty: the value of a pixel without a kept sample, in the mean and in the variance
+        :param var: also return the population variance (float32, not rooted); needs ``moments``
+        :param counts: also return ``coverage`` and ``kept``, the (OH, OW) int32 numbers of live and of kept samples
+        :param out: ``"host"``: numpy arrays; ``"device"``: torch tensors on the plan's device (the counts are copies of the state)
+        :return: ``mean``, or ``(mean[, var][, coverage, kept])``
+        """
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device', not %r" % (out,))
+        if var and not self.moments:
+            raise ValueError("the variance needs an accumulator made with moments=True")
+        plan = self.plan
+        oh, ow = self.out_shape
+        if out == "device":
+            import torch
+            mean = torch.empty((oh, ow), dtype=torch.float32, device=self._s1.device)
+            vplane = torch.empty((oh, ow), dtype=torch.float32, device=self._s1.device) if var else None
+            mptr, vptr = mean.data_ptr(), (vplane.data_ptr() if var else None)
+        else:
+            mean = plan._host_result((oh, ow), numpy.float32)
+            vplane = plan._host_result((oh, ow), numpy.float32) if var else None
+            mptr, vptr = mean.ctypes.data, (vplane.ctypes.data if var else None)
+        ms = C.c_double(0)
+        with plan._sem:
+            _lib.check(_lib.lib().siftmi_batch_stack_accum_result(
+                plan._handle, self._s1.data_ptr(), self._s2.data_ptr() if self.moments else None, self._kept.data_ptr(), ow, oh, mptr, vptr,
+                int(out == "device"), C.c_float(empty), C.byref(ms)))
+        res = (mean,) + ((vplane,) if var else ())
+        if counts:
+            if out == "device":
+                res += (self._coverage.clone(), self._kept.clone())
+            else:
+                res += (self._coverage.cpu().numpy(), self._kept.cpu().numpy())
+        return res if len(res) > 1 else mean
 
 
 def shard_indices(n_items, rank, world_size):

@@ -26,6 +26,7 @@
 #include "k_warp_cubic.hpp"
 #include "k_stack.hpp"
 #include "k_stack_clip.hpp"
+#include "k_stack_accum.hpp"
 #include "k_pyramid.hpp"
 #include "k_tail.hpp"
 #include "k_top_patch.hpp"
@@ -2130,14 +2131,16 @@ struct WarpIo {
 // and of a host result of `out_bytes`, the table of `n_images` frames as a pinned block and its device copy), the upload of
 // host frames -- one copy per run of frames that lie back to back in host memory (a stack is ONE copy) -- and of the table.
 int warp_begin(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, size_t px, void *out,
-               int32_t out_is_device, size_t out_bytes, const float *maps, const float *fills, int32_t mode, WarpIo *io) {
+               int32_t out_is_device, size_t out_bytes, const float *maps, const float *fills, int32_t mode, WarpIo *io,
+               bool state_is_device = false) {
     HIPCHK(hipSetDevice(b->device));
     siftmi_plan *p0 = b->lanes[0];
     hipStream_t stream = p0->stream;               // every lane is idle between two calls on the handle
     const int W = p0->W, H = p0->H;
     const size_t in_bytes = (size_t)W * H * px;
     // a device pointer on either side: ordered after what the caller's streams were given for it (siftmi.h, conventions)
-    if ((images_are_device && n_images > 0) || out_is_device) HIPCHK(hipDeviceSynchronize());
+    // (`state_is_device`: the call takes further device pointers, the planes of siftmi_batch_stack_accum[_result])
+    if ((images_are_device && n_images > 0) || out_is_device || state_is_device) HIPCHK(hipDeviceSynchronize());
     int rc;
     if (!images_are_device && (rc = grow_device(&b->warp_in, &b->warp_in_bytes, in_bytes * (size_t)n_images))) return rc;
     if (!out_is_device && (rc = grow_device(&b->warp_out, &b->warp_out_bytes, out_bytes))) return rc;
@@ -2236,6 +2239,34 @@ void launch_stack_clip(hipStream_t st, int reject, int interp, const WarpFrame *
         hipLaunchKernelGGL(stack_clip_kernel<SIFT_STACK_TRIM>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
     else
         hipLaunchKernelGGL(stack_clip_kernel<SIFT_STACK_SIGMA>, grid, block, lds, st, frames, S, p, out, coverage, kept, W, H, OW, OH, empty);
+}
+
+// The one launch site of the streaming accumulator (k_stack_accum.hpp): S >= 1 frames added into the caller's OH x OW state
+// planes.  s2 null: the instances without second moments; clip.center null: the instances without a clip.
+void launch_stack_accum(hipStream_t st, int interp, const WarpFrame *frames, int S, double *s1, double *s2, int32_t *coverage, int32_t *kept,
+                        const StackAccumClip &clip, int W, int H, int OW, int OH) {
+    const dim3 grid((unsigned)((OW + 63) / 64), (unsigned)((OH + 3) / 4)), block(64, 4);
+#define STACK_ACCUM_LAUNCH(CUBIC, MOMENTS, CLIP) \
+    hipLaunchKernelGGL((stack_accum_kernel<CUBIC, MOMENTS, CLIP>), grid, block, 0, st, frames, S, s1, s2, coverage, kept, clip, W, H, OW, OH)
+    const bool clipped = clip.center != nullptr;
+    if (interp == SIFTMI_INTERP_CUBIC) {
+        if (s2) { if (clipped) STACK_ACCUM_LAUNCH(true, true, true); else STACK_ACCUM_LAUNCH(true, true, false); }
+        else { if (clipped) STACK_ACCUM_LAUNCH(true, false, true); else STACK_ACCUM_LAUNCH(true, false, false); }
+    } else {
+        if (s2) { if (clipped) STACK_ACCUM_LAUNCH(false, true, true); else STACK_ACCUM_LAUNCH(false, true, false); }
+        else { if (clipped) STACK_ACCUM_LAUNCH(false, false, true); else STACK_ACCUM_LAUNCH(false, false, false); }
+    }
+#undef STACK_ACCUM_LAUNCH
+}
+
+// The one launch site of the accumulator's result (k_stack_accum.hpp): n >= 1 pixels of state to the mean and, unless null, the variance.
+void launch_stack_accum_result(hipStream_t st, const double *s1, const double *s2, const int32_t *kept, size_t n, float *mean, float *var,
+                               float empty) {
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (var)
+        hipLaunchKernelGGL(stack_accum_result_kernel<true>, grid, block, 0, st, s1, s2, kept, n, mean, var, empty);
+    else
+        hipLaunchKernelGGL(stack_accum_result_kernel<false>, grid, block, 0, st, s1, s2, kept, n, mean, var, empty);
 }
 
 // What every _ex entry refuses about its sampler before anything else is looked at: an unknown `interp`, and the cubic sampler with
@@ -2389,6 +2420,66 @@ int siftmi_batch_stack_clip_ex(siftmi_batch *b, const void *const *images, int32
     launch_stack_clip(io.stream, reject, interp, (const WarpFrame *)b->warp_tab, n_images, p, (float *)io.dst, cov, kep, io.W, io.H, OW, OH, empty);
     hipEventRecord(b->ev_wb, io.stream);
     return warp_end(b, io, out_is_device ? nullptr : out, plane, coverage, plane, kernel_ms, kept, plane);
+}
+
+// One chunk of a stack of any length warped and added into the caller's running sums (k_stack_accum.hpp).  Frames, maps, fills,
+// host staging and limits are siftmi_batch_stack_ex's: the same warp_begin / warp_end around the launch.  The state planes, the
+// centre and the variance are device pointers, so the call always synchronises the device once on entry.
+int siftmi_batch_stack_accum(siftmi_batch *b, const void *const *images, int32_t n_images, int32_t images_are_device, double *s1,
+                             double *s2, int32_t *coverage, int32_t *kept, int32_t OW, int32_t OH, const float *maps, const float *fills,
+                             int32_t mode, int32_t interp, const float *center, const float *var, float kappa_low, float kappa_high,
+                             double *kernel_ms) {
+    if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (int rc = check_interp(interp, mode, !b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8)) return rc;
+    if (n_images < 0) return fail(SIFTMI_EINVAL, "negative image count");
+    if (n_images > 65535) return fail(SIFTMI_EINVAL, "%d frames: more than 65535", n_images);
+    if (OW < 0 || OH < 0) return fail(SIFTMI_EINVAL, "negative output shape");
+    if (OH > 4 * 65535) return fail(SIFTMI_EINVAL, "output height %d: more than %d rows (4 per grid row)", OH, 4 * 65535);
+    if (!b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8) return fail(SIFTMI_EINVAL, "a batch created for RGB8 frames has no stack reduction");
+    if (!center != !var) return fail(SIFTMI_EINVAL, "a clip takes both the centre and the variance plane, or neither");
+    if (center && (!(kappa_low > 0.0f) || !(kappa_high > 0.0f)))
+        return fail(SIFTMI_EINVAL, "kappa_low %g, kappa_high %g: each must be > 0 (inf allowed)", kappa_low, kappa_high);
+    const bool nothing = n_images == 0 || OW == 0 || OH == 0;
+    if (n_images > 0 && (!images || !maps || !fills)) return fail(SIFTMI_EINVAL, "null argument");
+    if (!nothing && (!s1 || !coverage || !kept)) return fail(SIFTMI_EINVAL, "null state plane");
+    for (int32_t i = 0; i < n_images; i++) if (!images[i]) return fail(SIFTMI_EINVAL, "null image %d", i);
+    if (kernel_ms) *kernel_ms = 0;
+    if (nothing || b->lanes.empty()) return SIFTMI_OK;
+    WarpIo io;
+    int rc = warp_begin(b, images, n_images, images_are_device, sizeof(float), nullptr, 1, 0, maps, fills, mode, &io, true);
+    if (rc) return rc;
+    StackAccumClip clip{center, var, 0.0f, 0.0f};
+    if (center) { clip.kl2 = kappa_low * kappa_low; clip.kh2 = kappa_high * kappa_high; }
+    hipEventRecord(b->ev_wa, io.stream);
+    launch_stack_accum(io.stream, interp, (const WarpFrame *)b->warp_tab, n_images, s1, s2, coverage, kept, clip, io.W, io.H, OW, OH);
+    hipEventRecord(b->ev_wb, io.stream);
+    return warp_end(b, io, nullptr, 0, nullptr, 0, kernel_ms);
+}
+
+// The accumulator's sums turned into the mean and, unless null, the population variance (k_stack_accum.hpp).  A host result is
+// staged as siftmi_batch_stack's is: the mean, then the variance, in the batch's staging.
+int siftmi_batch_stack_accum_result(siftmi_batch *b, const double *s1, const double *s2, const int32_t *kept, int32_t OW, int32_t OH,
+                                    float *mean, float *var, int32_t out_is_device, float empty, double *kernel_ms) {
+    if (!b) return fail(SIFTMI_EINVAL, "null batch");
+    if (OW < 0 || OH < 0) return fail(SIFTMI_EINVAL, "negative output shape");
+    if (OH > 4 * 65535) return fail(SIFTMI_EINVAL, "output height %d: more than %d rows", OH, 4 * 65535);
+    if (!b->lanes.empty() && b->lanes[0]->dtype == SIFTMI_RGB8) return fail(SIFTMI_EINVAL, "a batch created for RGB8 frames has no stack reduction");
+    if (var && !s2) return fail(SIFTMI_EINVAL, "the variance needs the second moments (s2)");
+    const size_t n = (size_t)OW * OH;
+    if ((n + 255) / 256 > 2147483647u) return fail(SIFTMI_EINVAL, "%d x %d output pixels: more than one grid holds", OW, OH);
+    if (n && (!s1 || !kept)) return fail(SIFTMI_EINVAL, "null state plane");
+    if (n && !mean) return fail(SIFTMI_EINVAL, "null output");
+    if (kernel_ms) *kernel_ms = 0;
+    if (!n || b->lanes.empty()) return SIFTMI_OK;
+    const size_t plane = n * sizeof(float);
+    WarpIo io;
+    int rc = warp_begin(b, nullptr, 0, 0, sizeof(float), mean, out_is_device, plane * (var ? 2 : 1), nullptr, nullptr, 1, &io, true);
+    if (rc) return rc;
+    float *v = out_is_device ? var : (var ? reinterpret_cast<float *>((uint8_t *)io.dst + plane) : nullptr);
+    hipEventRecord(b->ev_wa, io.stream);
+    launch_stack_accum_result(io.stream, s1, s2, kept, n, (float *)io.dst, v, empty);
+    hipEventRecord(b->ev_wb, io.stream);
+    return warp_end(b, io, out_is_device ? nullptr : mean, plane, var, plane, kernel_ms);
 }
 
 int siftmi_plan_records_device(const siftmi_plan *p, const siftmi_keypoint **records, int64_t *count) {
